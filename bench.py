@@ -18,12 +18,19 @@ Strong scaling of a SMALL population — what the search actually issues (models
                   weighted BCE + F1-samples, fp16 taps, R=16, B=20, N = 15,552 / 2,608 (the MM-IMDB split sizes), --pop sampled
                   L=4 confs per GPU (weak scaling; default 512: the "memory-bound cell-kernel stress")
 
-The default line (workload c1, no workload flags) ALSO carries the search-sized workloads, measured after the timed region:
+A plain run sets up, warms up, times --steps steps and prints the line; nothing else is measured.  `--dump-outputs DIR` writes what
+the last timed step returned to its caller (the best dev metric of every candidate, in input order) as DIR/<metric>.npy (float64);
+with the same arguments the inputs and seeds are the same from run to run, so two builds can be compared output for output.
+
+`--full` adds everything else, measured after the timed region: the other initialisation path / sample order of the same workload
+(``config.other_init`` / ``other_order`` / ``other_both``), the stream probe (``roofline.stream_probe``), the CPU baselines
+(``cpu_baseline``, N = 1) and, on the default line (workload c1, no workload flags), the search-sized workloads:
   N = 1: ``config.small_pop = {"c2": {...}, "c3": {...}, "c1_single": {...}, "c1_pop6": {...}, "c1_pop12": {...}}`` — one call of 16 / 50 sampled L=4 confs at the search
          script's defaults (candidates/s, us per train step, schedule, nominal fraction of the HBM bound) and ONE conf-4 R=128
-         candidate (train steps/s: SURVEY.md 8d C2);
+         candidate (train steps/s: SURVEY.md 8d C2), and ``config.search_c3`` (the configs[3] search schedule end to end);
   N > 1: ``config.strong = {"c2": {...}, "c3": {...}}`` — the same two calls sharded over the ranks by the engine's own policy
          (per-rank seconds, per-rank shares, ranks the sharder used, the calibrated step-time model).
+The --no-* switches below leave out single parts of a --full run.
 
 Launch: ``python bench.py --gpus N`` (N > 1 and no WORLD_SIZE in the environment: bench.py starts its own N ranks under
 torch.distributed.run on 127.0.0.1 and exits non-zero if any of them fails) or
@@ -254,7 +261,14 @@ def main():
                          "uploaded); device = the engine's hash generator on the GPU")
     ap.add_argument("--engine-order", default="per_candidate", choices=["shared", "per_candidate"],
                     help="sample order: the reference's per-candidate shuffles (train_sampled_models' default), or one shuffle per epoch shared by the call's candidates")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline (other init / order, search-sized and strong-scaling workloads, the "
+                         "configs[3] search, the stream probe, CPU baselines); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-candidate best dev metric to DIR/<metric>.npy (float64)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_spawn(a.gpus))
     if a.workload in ("c2", "c3"):      # search-script defaults (main_searchable_ntu.py:26-47)
@@ -417,6 +431,11 @@ def main():
     dt = max(rank_dt)
     n_launch, ms, bytes_per_launch, sched = profile_summary()
     pops_per_step = len(NS.PROFILE) // max(a.steps, 1)       # populations one timed call trained (resident rounds: several)
+    if a.dump_outputs and rank == 0:
+        # what the last timed call returned to its caller: the best dev metric per candidate, in input order (all-gathered: every
+        # rank holds the whole list)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, ("best_dev_f1" if mm else "best_dev_acc") + ".npy"), np.asarray(accs, dtype=np.float64))
 
     def timed_calls(fn, reps):
         fn()                      # warm-up (layout decisions, first-touch of the population's pages, calibration of the sharder)
@@ -460,11 +479,11 @@ def main():
 
     small = strong = None
     plain = a.workload == "c1" and a.total_pop == 0 and not a.mixed_confs
-    if plain and world > 1 and not a.no_strong:
+    if a.full and plain and world > 1 and not a.no_strong:
         # Strong scaling next to the weak headline (outside the timed region): the search's own call sizes, sharded by the engine's
         # policy (mfas_amd/population.py: a call uses only as many ranks as its calibrated step-time model says pay)
         strong = {"c2": search_sized("c2", 16), "c3": search_sized("c3", 50)}
-    if plain and world == 1 and not a.no_small_pop and a.R == 128 and not a.no_bn:
+    if a.full and plain and world == 1 and not a.no_small_pop and a.R == 128 and not a.no_bn:
         small = {"c2": search_sized("c2", 16), "c3": search_sized("c3", 50)}
         # steps/s of the single found architecture — ONE conf-4 candidate (R=128, batchnorm, B=16), and the
         # share an 8-GPU search call leaves a rank at this R (6 candidates)
@@ -487,7 +506,7 @@ def main():
                            "schedule": psched, "frac_of_hbm_bound": cps * gb / (HBM_PEAK_GBS * 1e9),
                            "mean_best_dev_acc": float(np.mean(kaccs))}
     search_c3 = None
-    if plain and world == 1 and not a.no_small_pop and a.R == 128 and not a.no_bn and not a.no_search:
+    if a.full and plain and world == 1 and not a.no_small_pop and a.R == 128 and not a.no_bn and not a.no_search:
         # BASELINE configs[3] END TO END on this one GPU (outside the timed region, ~10 s): the reference's full EPNAS schedule at its own
         # search flags (main_searchable_ntu.py: --num_samples 50 --search_iterations 5 --max_fusions 4, R=16, B=20, drpt 0.5, no
         # batchnorm, E epochs per candidate) — 20 train_sampled_models calls, 982 candidates — with the seeded controller (surrogate on
@@ -513,7 +532,7 @@ def main():
                                  f"progression levels, R=16, B=20, no batchnorm, drpt {a.drpt}, E={a.epochs}, N_train={a.n_train}, N_dev={a.n_dev}), "
                                  f"seeded controller (seed 0), surrogate on {sa.controller_threads} CPU threads")
     other_init = other_order = other_both = None
-    if world == 1 and not a.no_small_pop and not a.mixed_confs:      # the same workload with the OTHER initialisation path / sample order, one call each
+    if a.full and world == 1 and not a.no_small_pop and not a.mixed_confs:      # the same workload with the OTHER initialisation path / sample order, one call each
         oargs = SimpleNamespace(**vars(args))
         oargs.engine_init = "device" if a.engine_init == "torch" else "torch"
         _, rt = timed_calls(lambda: train_fn(confs, stype, loaders, oargs, device), 1)
@@ -586,7 +605,7 @@ def main():
         # live rate of THIS box for a compute-free 3-plane read-modify-write probe (k_stream_probe), same units as `achieved`: a
         # reference point for box-to-box comparisons, NOT a ceiling — since the packed Adam the sweep itself is faster than the probe
         stream = None
-        if world == 1:
+        if a.full and world == 1:
             import ctypes
             from mfas_amd import _lib
             gb = ctypes.c_double(0)
@@ -628,7 +647,7 @@ def main():
                          "stream_probe": stream, "frac_of_stream_probe": (achieved / stream) if (achieved and stream) else None,
                          "mfma_util_pct_from_profile": mfma, "mfma_util_source": mfma_src},
         }
-        if world == 1 and not a.no_cpu_baseline and not mm:     # (the CPU restatements are NTU-shaped: the c5 line carries none)
+        if a.full and world == 1 and not a.no_cpu_baseline and not mm:     # (the CPU restatements are NTU-shaped: the c5 line carries none)
             line["cpu_baseline"] = cpu_baseline(train, dev, a)
         if out_fd is None:
             print(json.dumps(line), flush=True)

@@ -145,10 +145,28 @@ def put(out, key, arr):
         out[key + "#sum"] = np.array(arr.astype(np.float64).sum())
 
 
+MAX_FIXTURE = 1 << 20      # no committed file above 1 MiB: a larger fixture is split by key into <stem>.1.npz, <stem>.2.npz, ...
+
+
 def save(name, **arrs):
     path = os.path.join(HERE, name)
+    stem = path[:-len(".npz")]
+    for old in [path] + [f"{stem}.{i}.npz" for i in range(1, 64)]:
+        if os.path.exists(old):
+            os.remove(old)
     np.savez_compressed(path, **arrs)
-    print("wrote", name, os.path.getsize(path) // 1024, "KiB")
+    size = os.path.getsize(path)
+    if size > MAX_FIXTURE:              # (tests/helpers.py: load_npz merges the parts)
+        os.remove(path)
+        n = -(-size // (MAX_FIXTURE * 9 // 10))
+        keys = list(arrs)
+        for i in range(n):
+            part = f"{stem}.{i + 1}.npz"
+            np.savez_compressed(part, **{k: arrs[k] for k in keys[i::n]})
+            assert os.path.getsize(part) <= MAX_FIXTURE, part
+        print("wrote", name, "as", n, "parts")
+        return
+    print("wrote", name, size // 1024, "KiB")
 
 
 # ------------------------------------------------------------------ G1 scheduler

@@ -15,8 +15,27 @@ CONFS = {
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+def load_npz(path):
+    """np.load of a golden .npz.  A fixture above the 1 MiB limit for a committed file is stored split by key as <stem>.1.npz,
+    <stem>.2.npz, ... (tests/golden/make_golden.py: save) and merged back here into one {key: array} mapping."""
+    if os.path.exists(path):
+        return np.load(path)
+    stem = path[:-len(".npz")]
+    parts, i = [], 1
+    while os.path.exists(f"{stem}.{i}.npz"):
+        parts.append(f"{stem}.{i}.npz")
+        i += 1
+    if not parts:
+        raise FileNotFoundError(path)
+    merged = {}
+    for p in parts:
+        with np.load(p) as z:
+            merged.update({k: z[k] for k in z.files})
+    return merged
+
+
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name))
+    return load_npz(os.path.join(GOLDEN, name))
 
 
 def engine_hyper(ohp: "O.Hyper"):

@@ -43,7 +43,7 @@ def test_bench_starts_its_own_ranks(dev, world):
     import time
     pop = 3 if world < 8 else 1        # (8 ranks: what the driver's SCALE run starts on an 8-GPU node, here on one GPU)
     t0 = time.perf_counter()
-    line = run_bench(["--gpus", str(world), "--backend", "gloo", "--pop", str(pop), "--steps", "1", "--warmup", "1"] + TINY)
+    line = run_bench(["--gpus", str(world), "--backend", "gloo", "--pop", str(pop), "--steps", "1", "--warmup", "1", "--full"] + TINY)
     assert time.perf_counter() - t0 < 300.0
     assert line["n_gpus"] == world and line["config"]["rccl_ranks"] == world and line["config"]["backend"] == "gloo"
     assert line["scaling"] == "weak" and line["config"]["candidates_total_per_step"] == pop * world and line["value"] > 0
@@ -92,7 +92,7 @@ def test_bench_failing_rank_gives_nonzero_exit(dev):
 
 
 def test_bench_single_gpu_line_carries_the_search_sized_workloads(dev):
-    line = run_bench(["--pop", "4", "--steps", "1", "--warmup", "0"] + TINY)
+    line = run_bench(["--pop", "4", "--steps", "1", "--warmup", "0", "--full"] + TINY)
     assert line["n_gpus"] == 1 and line["metric"].startswith("candidate-archs trained/sec") and line["unit"] == "candidates/s"
     assert line["config"]["engine_init"] == "torch" and line["config"]["other_init"]["engine_init"] == "device"
     assert line["config"]["engine_order"] == "per_candidate" and line["config"]["other_order"]["engine_order"] == "shared"     # the reference's shuffles are the default
@@ -109,6 +109,26 @@ def test_bench_single_gpu_line_carries_the_search_sized_workloads(dev):
     one = sp["c1_single"]
     assert one["candidates"] == 1 and one["train_steps_per_s"] > 0 and one["kernel_us_per_train_step"] > 0 and one["schedule"]["groups"] == -1
     assert sp["c1_pop6"]["candidates"] == 6 and sp["c1_pop12"]["candidates"] == 12 and sp["c1_pop12"]["schedule"]["groups"] == 2
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_its_outputs(dev, tmp_path):
+    """Without --full the line carries the headline only; --steps sets the timed steps; --dump-outputs writes what the last timed
+    call returned (one best dev accuracy per candidate), the same in two runs with the same arguments."""
+    got = []
+    for run in ("a", "b"):
+        line = run_bench(["--pop", "5", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run)] + TINY)
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert abs(line["value"] - 5 * 2 / (line["ms_per_step"] * 2 / 1e3)) < 1e-6 * line["value"]
+        assert line["unit"] == "candidates/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        cfg = line["config"]
+        assert cfg["small_pop"] is None and cfg["search_c3"] is None and cfg["other_init"] is None and cfg["other_both"] is None
+        assert "cpu_baseline" not in line and line["roofline"]["stream_probe"] is None
+        assert sorted(os.listdir(tmp_path / run)) == ["best_dev_acc.npy"]
+        acc = np.load(tmp_path / run / "best_dev_acc.npy")
+        assert acc.dtype == np.float64 and acc.shape == (5,) and ((acc >= 0) & (acc <= 1)).all()
+        assert abs(float(acc.mean()) - cfg["mean_best_dev_acc"]) < 1e-12
+        got.append(acc)
+    assert np.array_equal(got[0], got[1])
 
 
 def test_bench_mmimdb_shaped_workload(dev):

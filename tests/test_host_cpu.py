@@ -503,3 +503,11 @@ def test_failed_rank_is_requeued_gloo(tmp_path):
         out, _ = p.communicate(timeout=180)
         assert p.returncode == 0, out.decode()
         assert b"requeue ok" in out
+
+
+def test_bench_options():
+    """bench.py offers --full (everything besides the headline) and --dump-outputs DIR, and refuses --steps 0 before touching a device."""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0 and "--full" in res.stdout and "--dump-outputs" in res.stdout, res.stdout[-2000:]
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 2 and "--steps must be at least 1" in res.stderr, res.stderr[-2000:]

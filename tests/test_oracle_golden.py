@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import np_oracle as O
+from tests.helpers import load_npz
 
 CONFS = {
     "c4": [[3, 1, 1], [1, 3, 0], [1, 1, 1], [3, 3, 0]],
@@ -25,7 +26,7 @@ VARIANTS = {
 
 
 def load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name))
+    return load_npz(os.path.join(golden_dir, name))
 
 
 def check(g, key, arr, rtol, atol, scale_atol=0.0, loose_atol=None):

@@ -3,7 +3,7 @@
 # MM-IMDB-shaped workload, PMC traffic / MFMA passes, population sweeps (R = 16 with / without BatchNorm, R = 128 with / without chain_split),
 # chain phase stamps.  Summaries are copied to profiles/r06_* by the builder.
 out=gpurun_out/r06; mkdir -p $out; export TMPDIR=/tmp
-timeout 900 python bench.py > $out/bench_pop128.log 2> $out/bench_pop128.err
+timeout 900 python bench.py --full > $out/bench_pop128.log 2> $out/bench_pop128.err
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/rp_bench -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-small-pop --no-search > $GRAFT_REPO_ROOT/$out/rp_bench.log 2>&1)
 timeout 600 python bench.py --workload c2 --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_c2_1gpu.log 2>&1
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/rp_c2 -o c2 -- python $GRAFT_REPO_ROOT/bench.py --workload c2 --steps 2 --warmup 1 --no-cpu-baseline > $GRAFT_REPO_ROOT/$out/rp_c2.log 2>&1)
