@@ -896,9 +896,6 @@ struct LeanRes {
 #define LEAN_BNV 400       // the cells' batch variance [cell][16] for the running statistics (chain_lean_tail)
 #define LEAN_SCR 1024      // floats: forward BN exchange [parity][sum | squares][tile][16] | +256: dgamma / dbeta [L][2][16] | +512: backward BN exchange | +768: [tile][cell][mean | rstd][16]
 
-#ifndef MFAS_RES_TRANSPOSED_SLABS
-#define MFAS_RES_TRANSPOSED_SLABS 1     // 0: debug build — the resident units keep the launch-per-phase operand order, the chain transposes in LDS
-#endif
 // LDS layout shared by chain_lean and the resident helpers
 template <int MB>
 struct LeanLds {
@@ -1059,8 +1056,7 @@ template <int MB, int MODE = 0, int PB = 16, int PLAIN = 0>
 __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& cs, const int bid, float* lds, const LeanPre& lp,
                                            const uint32_t keep_pre = 0u, const int lab_pre = 0) {
     constexpr bool COH = MODE >= 1;
-    constexpr bool RES = MODE == 2;
-    constexpr bool TS = RES && (MFAS_RES_TRANSPOSED_SLABS != 0);      // the partial slabs arrive transposed (resident units, persist.hip.h)
+    constexpr bool RES = MODE == 2;       // (resident units: the partial slabs arrive transposed, persist.hip.h)
 #ifdef MFAS_CHAIN_TIMING
     const unsigned long long ct0 = __builtin_readcyclecounter();
 #endif
@@ -1119,7 +1115,7 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
         // the compiler threads "slab 0 exists" through to its consumption: it waited for slab 0 before requesting slab 1)
         // (transposed slabs: a lane's item is ONE batch row — rows beyond the batch hold zeros nobody needs to move: with B = 20 the
         //  second tile's slab items are 3/4 padding, 37 % of the slab bytes that all cross this one CU's memory pipeline)
-        int nch_v = (!TS || (pit >> 6) * 16 + l15 < nvalid) ? nch : 0;
+        int nch_v = (pit >> 6) * 16 + l15 < nvalid ? nch : 0;
         asm volatile("" : "+v"(nch_v));
 #pragma unroll
         for (int u = 0; u < PB; ++u) {
@@ -1212,7 +1208,7 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
                 }
         }
         // resident: cell 0's sums stay in the tile waves' registers (transposed slabs: the item IS the lane's register image)
-        if (!(TS && pi == 0)) {
+        if (!(RES && pi == 0)) {
             if (f_alphas) {
                 *reinterpret_cast<f32x4*>(yf_l + tid * 4) = accS;
                 *reinterpret_cast<f32x4*>(yf_l + sav_plane + tid * 4) = accV;
@@ -1227,8 +1223,6 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
         *reinterpret_cast<f32x4*>(ll.own + (wave << 8) + lane * 4) = st0;
         if (wave + 1 < LEAN_OWN_TILES) *reinterpret_cast<f32x4*>(ll.own + ((LEAN_OWN_TILES + wave + 1) << 8) + lane * 4) = st1;
         lds_barrier();
-    } else if constexpr (!TS) {
-        lds_barrier();
     }
     const float* vecW = vec_l;
     CT_STAMP(0);
@@ -1236,7 +1230,7 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
     // reduced feature sums of (cell i, this tile) in the transposed register image: S and V parts
     auto cell_sums = [&](const int i, f32x4& yS, f32x4& yV) {
         const int o = (i * MB + wave) << 8;
-        if constexpr (TS) {
+        if constexpr (RES) {
             yS = *reinterpret_cast<const f32x4*>(yf_l + o + lane * 4);
             if (f_alphas) yV = *reinterpret_cast<const f32x4*>(yf_l + sav_plane + o + lane * 4);
         } else {
@@ -1299,7 +1293,7 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
                     stc1<COH>(sb + g.sb_gsc + i * 2 + 1, sgV);
                 }
             }
-            if constexpr (TS) {
+            if constexpr (RES) {
                 if (i == 1) lds_barrier();     // the other waves' sums of cells 1..L-1 are in LDS (they got there under cell 0)
             }
             if constexpr (RES && PLAIN != 2) {
@@ -1314,7 +1308,7 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
             f32x4 v = z4, s1 = z4;
             if (is_tw) {
                 f32x4 yS = accS, yV = accV;
-                if (!TS || i > 0) { yS = z4; yV = z4; cell_sums(i, yS, yV); }
+                if (!RES || i > 0) { yS = z4; yV = z4; cell_sums(i, yS, yV); }
                 else if (!f_alphas) yS = accS + accV;
                 f32x4 acc = yS;
                 CT_SUM4(i, acc);

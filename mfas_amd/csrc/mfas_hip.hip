@@ -72,8 +72,6 @@ __global__ void __launch_bounds__(STEP_THREADS, WPE) k_step(const StepArgs a) {
     }
     else if (bid < a.nchain + a.ga.nblocks) gather_body(a.ga, a.ga.cands[bid - a.nchain], a.sa.g, a.sa.tab, a.sa.order, (int)threadIdx.x);
     else if (bid < a.nchain + a.ga.nblocks + a.sa.ntap) sweep_tap_body<MB, NT, SweepU<MB, WPE>::v>(a.sa, bid - a.nchain - a.ga.nblocks, lds);
-    else if (!LEAN && a.sa.desc[bid - a.nchain - a.ga.nblocks - a.sa.ntap].nsub > 1)      // multi-chunk feature unit (general chain, 8 row blocks)
-        sweep_multi_body<MB, NT, SweepU<MB, WPE>::v>(a.sa, sweep_step_of(a.sa), bid - a.nchain - a.ga.nblocks - a.sa.ntap, lds);
     else sweep_body<MB, NT, SweepU<MB, WPE>::v>(a.sa, sweep_step_of(a.sa), bid - a.nchain - a.ga.nblocks - a.sa.ntap, lds);
 }
 
@@ -113,21 +111,16 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
 // and kept in the population: nothing else in this translation unit calls getenv, so a variable that changes after create() cannot
 // change the schedule of a population that was laid out (and parity-tested) without it.  An empty environment gives the defaults
 // below = the configuration the test suites run; INTEGRATION.md lists the switches, mfas_tuning_describe() prints the parsed set
-// (tests/test_host_cpu.py::test_empty_environment_selects_the_tested_defaults).  They are A/B and debugging aids, not API.
+// (tests/test_host_cpu.py::test_switches_default_when_unset_and_retired_ones_are_ignored).  They are A/B and debugging aids, not API.
 // ================================================================================================
 struct Tuning {
     int persist = -1;               // MFAS_PERSIST            0: never take the resident schedule (k_president); unset / 1: where it fits
     int no_lean_chain = 0;          // MFAS_NO_LEAN_CHAIN      general chain_body also at R <= 16
-    int persist_no_resident = 0;    // MFAS_PERSIST_NO_RESIDENT   } either one: no resident units, i.e. launch per phase
-    int persist_no_res_chain = 0;   // MFAS_PERSIST_NO_RES_CHAIN  }
-    int subchunks = 0;              // MFAS_SUBCHUNKS=n        multi-chunk sweep units (measured negative, opt-in)
-    int subchunk_skip = 0;          // MFAS_SUBCHUNK_SKIP=n    every n-th candidate keeps one-chunk units
     int groups = 0;                 // MFAS_GROUPS=1|2         force one / two candidate groups (0: by population size)
     int same_group = -1;            // MFAS_SAME_GROUP         0: never k_step_same, 2: whatever the size (-1: by state bytes)
     int no_tap_major = 0;           // MFAS_NO_TAP_MAJOR       per-segment sweep units also at R < 128
     int force_tap_major = 0;        // MFAS_FORCE_TAP_MAJOR    tap-major units even with < 192 workgroups
     int no_red_in_sweep = 0;        // MFAS_NO_RED_IN_SWEEP    the chain reduces the partial slabs itself
-    int force_red_in_sweep = 0;     // MFAS_FORCE_RED_IN_SWEEP reduce-in-sweep whatever the population size (A/B: measured negative at 128 candidates)
     double occ_bytes = -1.0;        // MFAS_OCC_BYTES          MB == 2: crossover between the 2- and 4-waves-per-SIMD sweep builds
     int no_xcd_placement = 0;       // MFAS_NO_XCD_PLACEMENT   resident launch: block b runs role b
     int n_xcd = 0;                  // MFAS_XCDS=n             XCDs the placement assumes (0: 8 — MI355X in SPX mode)
@@ -142,7 +135,7 @@ struct Tuning {
     int no_plain_chain = 0;         // MFAS_NO_PLAIN_CHAIN     resident chain: the general (BN / alphas / multitask capable) instantiation
     int persist_verbose = 0;        // MFAS_PERSIST_VERBOSE=1|2
     int prof_every = 16;            // MFAS_PROF_EVERY=n       HIP events around every n-th sweep launch when profiling is on
-    int chain_split = -1;           // MFAS_CHAIN_SPLIT=0|2|4  R = 128 general chain over that many CUs per candidate (-1: the planner decides)
+    int chain_split = -1;           // MFAS_CHAIN_SPLIT        0 or 1: the one-CU chain_body; unset / other values: the planner decides (4 CUs or 1)
     // test hooks: parsed only by the -DMFAS_TEST_HOOKS build variant (__graft_entry__.build_variant("hooks", ...)); the product library
     // never reads these variables
     int test_not_resident = -1;     // MFAS_PERSIST_TEST_NOT_RESIDENT=e   every roll call from epoch e on "fails"
@@ -155,16 +148,11 @@ static Tuning tuning_from_env() {
     auto num = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
     t.persist = getenv("MFAS_PERSIST") ? (atoi(getenv("MFAS_PERSIST")) != 0 ? 1 : 0) : -1;
     t.no_lean_chain = flag("MFAS_NO_LEAN_CHAIN");
-    t.persist_no_resident = flag("MFAS_PERSIST_NO_RESIDENT");
-    t.persist_no_res_chain = flag("MFAS_PERSIST_NO_RES_CHAIN");
-    t.subchunks = num("MFAS_SUBCHUNKS", 0);
-    t.subchunk_skip = num("MFAS_SUBCHUNK_SKIP", 0);
     t.groups = num("MFAS_GROUPS", 0);
     t.same_group = num("MFAS_SAME_GROUP", -1);
     t.no_tap_major = flag("MFAS_NO_TAP_MAJOR");
     t.force_tap_major = flag("MFAS_FORCE_TAP_MAJOR");
     t.no_red_in_sweep = flag("MFAS_NO_RED_IN_SWEEP");
-    t.force_red_in_sweep = flag("MFAS_FORCE_RED_IN_SWEEP");
     if (const char* e = getenv("MFAS_OCC_BYTES")) t.occ_bytes = atof(e);
     t.no_xcd_placement = flag("MFAS_NO_XCD_PLACEMENT");
     t.n_xcd = num("MFAS_XCDS", 0);
@@ -193,12 +181,12 @@ extern "C" int mfas_tuning_describe(char* buf, int32_t cap) {
     const Tuning t = tuning_from_env();
     char tmp[1024];
     snprintf(tmp, sizeof(tmp),
-             "persist=%d no_lean_chain=%d persist_no_resident=%d persist_no_res_chain=%d subchunks=%d subchunk_skip=%d groups=%d same_group=%d "
-             "no_tap_major=%d force_tap_major=%d no_red_in_sweep=%d force_red_in_sweep=%d occ_bytes=%g no_xcd_placement=%d n_xcd=%d persist_trace=%d nt=%d eval_no_x16=%d "
+             "persist=%d no_lean_chain=%d groups=%d same_group=%d "
+             "no_tap_major=%d force_tap_major=%d no_red_in_sweep=%d occ_bytes=%g no_xcd_placement=%d n_xcd=%d persist_trace=%d nt=%d eval_no_x16=%d "
              "eval_no_msplit=%d eval_no_b3=%d eval_no_wl=%d no_gather=%d gather_verbose=%d no_plain_chain=%d persist_verbose=%d prof_every=%d "
              "chain_split=%d test_not_resident=%d test_lose_step=%d hooks=%d",
-             t.persist, t.no_lean_chain, t.persist_no_resident, t.persist_no_res_chain, t.subchunks, t.subchunk_skip, t.groups, t.same_group,
-             t.no_tap_major, t.force_tap_major, t.no_red_in_sweep, t.force_red_in_sweep, t.occ_bytes, t.no_xcd_placement, t.n_xcd, t.persist_trace, t.nt, t.eval_no_x16,
+             t.persist, t.no_lean_chain, t.groups, t.same_group,
+             t.no_tap_major, t.force_tap_major, t.no_red_in_sweep, t.occ_bytes, t.no_xcd_placement, t.n_xcd, t.persist_trace, t.nt, t.eval_no_x16,
              t.eval_no_msplit, t.eval_no_b3, t.eval_no_wl, t.no_gather, t.gather_verbose, t.no_plain_chain, t.persist_verbose, t.prof_every,
              t.chain_split, t.test_not_resident, t.test_lose_step,
 #ifdef MFAS_TEST_HOOKS
@@ -232,8 +220,6 @@ struct mfas_population {
     int64_t plane_stride = 0, wt_size = 0, step_total = 0;
     CandDev* d_cands = nullptr;
     SegDesc* d_descs = nullptr;
-    SegDesc* d_mdescs = nullptr;         // the same units as the sweep streams them (multi-chunk units merged), candidate-major
-    std::vector<int> mdesc_start;        // K+1
     struct Group { int c0 = 0, nc = 0, ndesc = 0, ntap = 0; SegDesc* d_descs = nullptr; TapDesc* d_taps = nullptr;
                    double alg_state = 0, alg_feat = 0; };
     std::vector<Group> groups;           // 1 or 2 contiguous candidate ranges, each with its own sweep work list
@@ -262,7 +248,6 @@ struct mfas_population {
     bool persist = false;
     int n_cus = 0;
     uint32_t* d_red_cnt = nullptr;  // reduce-in-sweep arrival counters [K][4] (small populations, general chain)
-    int lp_group = 1;               // chunks per sweep unit of this layout (multi-chunk units: opt-in)
     char* d_gather = nullptr;       // gathered rows [K][2 parities][taps][Bp][width] (two-group schedule, per-candidate orders; sweep.hip.h)
     size_t gather_cap = 0;
     bool red_in_sweep = false;
@@ -353,8 +338,6 @@ struct LayoutPlan {
     bool res_ok = false, res_wide = false, lean_ok = false;
     int nres_wg = 0;
     bool resident = false;           // the resident persistent schedule runs (before the byte-size limits, which no resident population reaches)
-    int group = 1;                   // consecutive column chunks one sweep workgroup streams (SegDesc::nsub): ONE forward partial slab per group
-    int group_skip = 0;              // (experiment, MFAS_SUBCHUNK_SKIP=n) every n-th candidate keeps one-chunk units: a fine-grained tail for the work list
 };
 
 static size_t plan_res_lds(const mfas_hyper* hp, const Geo& g, int cc, int nu) {
@@ -382,7 +365,7 @@ static void plan_layout(const mfas_hyper* hp, const Geo& g, const int32_t* confs
                                + (size_t)(g.alphas ? 2 : 1) * MFAS_MAX_CELLS * g.MB * 256 + (size_t)3 * (MFAS_MAX_CELLS * g.vec_cell_stride + g.Cp)
                                + LEAN_SCR + 8 + LeanLds<1>::stage_floats() + (size_t)g.Bp * 64) * 4;
     lp.lean_ok = g.nrb == 1 && g.ncb <= 4 && g.MB <= 2 && lean_bytes <= 78 * 1024 && !tu.no_lean_chain;
-    lp.plan_res = lp.want_persist && g.nrb == 1 && g.MB <= 2 && !tu.persist_no_resident && !tu.persist_no_res_chain && lp.lean_ok;
+    lp.plan_res = lp.want_persist && g.nrb == 1 && g.MB <= 2 && lp.lean_ok;
     auto feat_units = [&](int cc_target, int* max_cc) {
         int64_t n = 0;
         int mx = 0;
@@ -438,18 +421,6 @@ static void plan_layout(const mfas_hyper* hp, const Geo& g, const int32_t* confs
         lp.target = target;
     }
     lp.target = std::max(16, (lp.target / 16) * 16);
-    // Multi-chunk units (round 4): where the planner streams 64-column chunks (R >= 128, >= 28 candidates: the finest, best-balanced
-    // walk of W / m / v) a workgroup takes `group` consecutive chunks and keeps the forward partial sums in registers across them —
-    // the memory walk stays that of 64-column chunks, the partial slabs (8 KB written by the unit and read back by the chain, per
-    // chunk: 8 % of the algorithmic bytes of a conf-4 step at R = 128) and the dy staging shrink by the group factor.  A caller who
-    // fixes chunk_cols gets exactly that decomposition (group 1).
-    lp.group = 1;
-    // (exactly 8 row blocks: wave = row block, one accumulator per wave; K >= 28: neither the same-group launch nor reduce-in-sweep)
-    // (measured, profiles/r04_subchunks.log: uniform groups of 2 / 4 / 8 / 16 chunks are SLOWER — 314 / 320 / 327 / 327 us per launch
-    //  against 299 on the same box — because 4x larger units leave ~4 units per workgroup slot and the launch's tail grows faster
-    //  than the slab traffic shrinks: the default stays one chunk per unit, MFAS_SUBCHUNKS / MFAS_SUBCHUNK_SKIP select the other forms)
-    if (tu.subchunks > 0 && g.nrb == STEP_NW && K >= 28 && !lp.plan_res) lp.group = std::max(1, std::min(64, tu.subchunks));
-    lp.group_skip = tu.subchunk_skip;
     {
         int mx = 0;
         lp.nfeat = (int)feat_units(lp.target, &mx);
@@ -489,25 +460,6 @@ static int validate_inputs(const mfas_hyper* hp, const int32_t* confs, const int
         }
     }
     return MFAS_OK;
-}
-
-// The sweep's work list: consecutive chunk descriptors of one feature segment that share a partial slab (part_idx) become ONE
-// unit that streams them one after the other (SegDesc::nsub); k_pack / the resident schedule keep the per-chunk descriptors.
-static std::vector<SegDesc> merge_units(const std::vector<SegDesc>& in) {
-    std::vector<SegDesc> out;
-    for (const SegDesc& d : in) {
-        if (!out.empty()) {
-            SegDesc& b = out.back();
-            if (d.kind <= KIND_V && b.kind == d.kind && b.cand == d.cand && b.cell == d.cell && b.part_idx == d.part_idx && b.cc == d.cc &&
-                b.k0 + b.nsub * b.cc == d.k0 && b.w_off + (int64_t)b.nsub * b.rows_p * b.cc == d.w_off) {
-                b.nsub++;
-                continue;
-            }
-        }
-        out.push_back(d);
-        if (out.back().nsub < 1) out.back().nsub = 1;
-    }
-    return out;
 }
 
 #define MFAS_RETRY_NO_PERSIST 12345   // internal: the layout was planned for the resident persistent schedule, which then did not fit
@@ -609,13 +561,11 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
                 const int cols_p = widths[j];
                 const int cc = j < 2 ? pick_chunk(cols_p, target) : cols_p;
                 const int nch = cols_p / cc;
-                const int grp = (j < 2 && (lp.group_skip <= 0 || (k % lp.group_skip) != lp.group_skip - 1)) ? lp.group : 1;   // chunks per sweep unit = per partial slab
-                const int nun = (nch + grp - 1) / grp;
                 c.seg_off[i][j] = plane_off;
                 c.seg_cc[i][j] = cc;
                 c.seg_cols[i][j] = cols_p;
-                if (j == 0) c.nch_s[i] = nun;
-                if (j == 1) c.nch_v[i] = nun;
+                if (j == 0) c.nch_s[i] = nch;
+                if (j == 1) c.nch_v[i] = nch;
                 if (j == 2) { c.outT_off[i] = wt_off; }
                 for (int ch = 0; ch < nch; ++ch) {
                     SegDesc d;
@@ -624,15 +574,14 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
                     d.k0 = ch * cc; d.cc = cc; d.rows_p = g.Rp; d.width = j < 2 ? widths[j] : g.Rp;
                     d.w_off = plane_off + (int64_t)ch * g.Rp * cc;
                     d.wt_off = j == 2 ? wt_off : -1;
-                    d.part_idx = j < 2 ? (j == 0 ? ch / grp : c.nch_s[i] + ch / grp) : 0;
-                    d.nsub = 1;
+                    d.part_idx = j < 2 ? (j == 0 ? ch : c.nch_s[i] + ch) : 0;     // one partial slab per chunk
                     d.rows = hp->R; d.cols = true_w[j];
                     d.src_off = c.f_W[i]; d.src_ld = Kin; d.src_col0 = col0[j];
                     d.init_seed = 2 * i; d.init_bound = bound;
                     d.rb0 = 0; d.seg_nrb = g.nrb;
                     p->descs.push_back(d);
                 }
-                if (j < 2) pslot += nun;
+                if (j < 2) pslot += nch;
                 plane_off += (int64_t)g.Rp * cols_p;
                 if (j == 2) wt_off += (int64_t)g.Rp * g.Rp;
                 alg_bytes += 24.0 * hp->R * true_w[j];
@@ -653,7 +602,7 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
             d.rows = hp->C; d.cols = hp->R;
             d.src_off = c.f_Wc; d.src_ld = hp->R; d.src_col0 = 0;
             d.init_seed = 10; d.init_bound = (float)(1.0 / sqrt((double)hp->R));
-            d.rb0 = 0; d.seg_nrb = g.ncb; d.nsub = 1;
+            d.rb0 = 0; d.seg_nrb = g.ncb;
             p->descs.push_back(d);
             plane_off += (int64_t)g.Cp * g.Rp;
             wt_off += (int64_t)g.Cp * g.Rp;
@@ -769,19 +718,6 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
     }
     CREATE_CHK(hipMemcpy(p->d_cands, p->cands.data(), sizeof(CandDev) * K, hipMemcpyHostToDevice));
     CREATE_CHK(hipMemcpy(p->d_descs, p->descs.data(), sizeof(SegDesc) * p->descs.size(), hipMemcpyHostToDevice));
-    {
-        std::vector<SegDesc> merged;
-        p->mdesc_start.assign(K + 1, 0);
-        for (int k = 0; k < K; ++k) {
-            p->mdesc_start[k] = (int)merged.size();
-            std::vector<SegDesc> one(p->descs.begin() + p->desc_start[k], p->descs.begin() + p->desc_start[k + 1]);
-            if (lp.group > 1) one = merge_units(one);
-            merged.insert(merged.end(), one.begin(), one.end());
-        }
-        p->mdesc_start[K] = (int)merged.size();
-        CREATE_CHK(hipMalloc(&p->d_mdescs, sizeof(SegDesc) * merged.size()));
-        CREATE_CHK(hipMemcpy(p->d_mdescs, merged.data(), sizeof(SegDesc) * merged.size(), hipMemcpyHostToDevice));
-    }
     {   // candidate groups: two halves balanced by work (descriptor columns), contiguous ranges
         // Two groups (the chain of one runs under the sweep of the other).  Measured on MI355X (cand/s, unfused vs fused):
         // general chain, R=128: 16 candidates 104 vs 96, 20: 103 vs 110, 32: 119 vs 142 -> fused from 20;
@@ -810,8 +746,7 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
             double state_bytes = 0;
             for (const SegDesc& d : p->descs) state_bytes += 24.0 * d.cc * d.rows_p;
             const bool two_forced = tu.groups >= 2;      // (tests: the two-group fused schedule)
-            p->same_group = !p->persist && !p->lean_chain && g.MB <= 2 && (state_bytes <= 260e6 || sgenv == 2) && sgenv != 0 && !two_forced &&
-                            lp.group == 1;      // (multi-chunk units exist in k_step's sweep only)
+            p->same_group = !p->persist && !p->lean_chain && g.MB <= 2 && (state_bytes <= 260e6 || sgenv == 2) && sgenv != 0 && !two_forced;
         }
         if (p->same_group) ngroups = 1;
         // the chain of one candidate over 4 CUs (chain.hip.h, chain_split): eight row blocks, one batch tile, <= 4 class blocks, no alphas
@@ -819,7 +754,6 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
         // against a 47 us chain; beyond, the chain hides under the other group's sweep and 4 x 64 chain workgroups would only take CUs from it)
         p->chain_split = ((p->same_group || (ngroups == 2 && K < 28)) && !p->lean_chain && !p->persist && g.MB == 1 && g.nrb == 8 && g.ncb <= 4 && !g.alphas &&
                           tu.chain_split != 0 && tu.chain_split != 1) ? 4 : 0;
-        p->lp_group = lp.group;
         int split = K;
         if (ngroups == 2) {
             double tot = 0, run = 0;
@@ -840,7 +774,6 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
                 gr.alg_state += 24.0 * d.rows * std::max(0, std::min(d.cc, d.cols - d.k0));
                 if (d.kind <= KIND_V) gr.alg_feat += (double)hp->B * d.cc;
             }
-            if (lp.group > 1) all = merge_units(all);
             // small R (1, 2 or 4 row blocks): feature segments are regrouped tap-major (sweep_tap_body)
             std::vector<SegDesc> sorted;
             std::vector<TapDesc> taps;
@@ -879,7 +812,7 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
                 sorted = all;
             }
             std::stable_sort(sorted.begin(), sorted.end(), [](const SegDesc& x, const SegDesc& y) {
-                return (int64_t)x.cc * x.rows_p * std::max(1, x.nsub) > (int64_t)y.cc * y.rows_p * std::max(1, y.nsub); });
+                return (int64_t)x.cc * x.rows_p > (int64_t)y.cc * y.rows_p; });
             if (p->same_group) {
                 // OUT / HEAD units one ROW BLOCK each (round 6): as ONE workgroup per 128 x 128 segment every wave walked its row block's eight
                 // tiles in four dependent load -> Adam -> store rounds of ~2.5 us behind the dy it waits for — OUT_1, released by the LAST dy of
@@ -920,7 +853,7 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
     // (not with chain_split: the reducing unit's drain + arrival + summing pass behind the LAST dy of the step ends the launch 3.5 us later,
     //  while the chain's four parts sum their own row blocks of the slabs at entry, every load in flight at once; measured, K = 1: 41.3 with
     //  the reduction in the sweep, 38.4 without, 43.0 with a hybrid — cells >= 1 in the sweep, cell 0 in the chain — profiles/r06_chain_split_r128.log)
-    p->red_in_sweep = (K < 28 || tu.force_red_in_sweep) && !p->lean_chain && !p->persist && !tu.no_red_in_sweep && !(p->chain_split && p->same_group);
+    p->red_in_sweep = K < 28 && !p->lean_chain && !p->persist && !tu.no_red_in_sweep && !(p->chain_split && p->same_group);
     for (const auto& gr : p->groups) if (gr.ntap != 0) p->red_in_sweep = false;     // (tap-major workgroups serve several candidates)
     if (p->red_in_sweep) {
         CREATE_CHK(hipMalloc(&p->d_red_cnt, sizeof(uint32_t) * K * MFAS_MAX_CELLS));
@@ -1080,7 +1013,7 @@ extern "C" void mfas_population_destroy(mfas_population* p) {
     for (hipEvent_t e : p->ev) hipEventDestroy(e);
     hipFree(p->plane); hipFree(p->wt); hipFree(p->stepbuf); hipFree(p->best);
     for (auto& gr : p->groups) { hipFree(gr.d_descs); hipFree(gr.d_taps); }
-    hipFree(p->d_cands); hipFree(p->d_descs); hipFree(p->d_mdescs); hipFree(p->d_stats); hipFree(p->d_status);
+    hipFree(p->d_cands); hipFree(p->d_descs); hipFree(p->d_stats); hipFree(p->d_status);
     hipFree(p->d_seeds); hipFree(p->d_corr); hipFree(p->d_posw);
     hipFree(p->d_red_cnt);
     hipFree(p->d_gather);
@@ -1448,7 +1381,7 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
     bool use_gather = false;
     int64_t g_par_stride = 0, g_cand_stride = 0;
     auto setup_gather = [&]() -> hipError_t {
-        use_gather = NG == 2 && !p->persist && order && p->g.order_stride > 0 && p->lp_group == 1 && !p->tune.no_gather;
+        use_gather = NG == 2 && !p->persist && order && p->g.order_stride > 0 && !p->tune.no_gather;
         if (!use_gather) return hipSuccess;
         int64_t totw = 0;
         for (int u = 0; u < MFAS_MAX_TAPS; ++u) totw += p->g.sw[u] + p->g.vw[u];
@@ -1861,13 +1794,13 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
     memset(&st, 0, sizeof(st));
     st.sa.cands = p->d_cands; st.sa.plane = p->plane; st.sa.plane_stride = p->plane_stride; st.sa.wt = p->wt;
     st.sa.stepbuf = p->stepbuf; st.sa.tab = *tab; st.sa.order = nullptr; st.sa.g = g; st.sa.g.order_stride = 0;
-    st.sa.desc = p->d_mdescs + p->mdesc_start[k]; st.sa.tdesc = nullptr; st.sa.ntap = 0;
+    st.sa.desc = p->d_descs + p->desc_start[k]; st.sa.tdesc = nullptr; st.sa.ntap = 0;
     st.sa.do_update = 0; st.sa.do_forward = 1;
     st.sa.pos_n = row0; st.sa.base_n = (int)row0; st.sa.nvalid_n = nrows;
     st.sa.pos_t = row0; st.sa.base_t = (int)row0; st.sa.nvalid_t = nrows;
     st.sa.ac = ac;
     st.nchain = 0;
-    const unsigned nsw = (unsigned)(p->mdesc_start[k + 1] - p->mdesc_start[k]);
+    const unsigned nsw = (unsigned)(p->desc_start[k + 1] - p->desc_start[k]);
     size_t lds_need = p->lds_step;   // (a population laid out for resident units budgets its streaming LDS without them)
     for (int j = p->desc_start[k]; j < p->desc_start[k + 1]; ++j) {
         const SegDesc& d = p->descs[j];

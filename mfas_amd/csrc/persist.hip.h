@@ -132,31 +132,19 @@ __device__ __forceinline__ void stage_table16(uint16_t* dst, int S16, const void
     }
 }
 
-// LDS-DMA staging of 16-bit table rows (round 4; OPT-IN: the -DMFAS_RES_DMA=1 build variant, __graft_entry__.build_variant("dma", ...)).
-// Measured on MI355X (profiles/r04_resident_lds_dma_ab.log): +1-2 % at 24-28 equal-sized candidates, but -4...-10 % (and noisy) on
-// mixed-depth populations of 28 — what the search issues — and nothing below 16 candidates: the default stays the cooperative
-// register staging.  Each wave stages exactly
-// the k-blocks IT multiplies with — one `global_load_lds_dwordx4` per k-block and batch: 32 rows x 32 bytes = the 64 lanes' 16-byte
-// pieces, landing contiguously in a k-block-major LDS image [kb][row][16 halves] — so the copy needs no VGPRs, no LDS-store pass and
-// NO workgroup barrier (a wave only ever reads what it wrote itself), and it is asynchronous: issued right after a unit's step, it
-// lands while the workgroup already serves its other unit or waits for the chain.  Rows beyond the batch read a zeroed line.
-// (M0 = the wave-uniform LDS destination; saved and restored inside the statement: cdna_hip_programming.md, LDS-DMA recipe.)
+// LDS-DMA copy of 16 bytes per lane (`global_load_lds_dwordx4`: the 64 lanes' pieces land contiguously at the wave-uniform LDS
+// address lds_dst).  The dev pass (eval.hip.h, WL walk) copies its weight tiles with it — a 1 KB tile per call, no VGPRs, no LDS-store
+// pass; the copy is invisible to the compiler's counters, so the caller waits for it with an explicit s_waitcnt vmcnt.
+// (M0 = the LDS destination; saved and restored inside the statement.)
 __device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds_dst) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
-#ifndef MFAS_RES_DMA
-#define MFAS_RES_DMA 0
-#endif
 
 // forward partial of a resident unit: operands SWAPPED -> the slab is the partial's TRANSPOSE, chain_lean's register image (the
 // f32 MFMA is symmetric under the swap bit for bit: tools/mfma_swap_check.hip)
-#if MFAS_RES_TRANSPOSED_SLABS
 #define RES_FWD_MFMA(x, w, acc) MFMA16((w), (x), (acc))
-#else
-#define RES_FWD_MFMA(x, w, acc) MFMA16((x), (w), (acc))
-#endif
 struct ResUnit {              // wave-uniform constants of one resident unit
     int32_t valid, index, cand, cell, kind, cc, nkb, S, width, k0;
     const void* tp;
@@ -222,44 +210,21 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
     const float a_w1 = sa.ac.w1, a_b2 = sa.ac.b2, a_w2 = sa.ac.w2, a_eps = sa.ac.eps, a_wd = sa.ac.wd;   // scalars, not a struct copy (common.hip.h adam4)
 
     // MFMA operand reads from a staged batch: one element (dW: A[i = column][k = batch row]) / four consecutive columns
-    constexpr bool DMA = X16 && (MFAS_RES_DMA != 0);      // k-block-major image [kb][row][16], staged per wave by LDS-DMA
     auto x1 = [&](const float* xb, int S, int row, int col) -> float {
-        if constexpr (DMA) return cvt16(as_lds(reinterpret_cast<const uint16_t*>(xb))[(((col >> 4) * Bp + row) << 4) + (col & 15)], dt);
-        else if constexpr (X16) return cvt16(as_lds(reinterpret_cast<const uint16_t*>(xb))[row * S + col], dt);
+        if constexpr (X16) return cvt16(as_lds(reinterpret_cast<const uint16_t*>(xb))[row * S + col], dt);
         else return as_lds(xb)[row * S + col];
     };
     auto x4of = [&](const float* xb, int S, int row, int col) -> f32x4 {
         if constexpr (X16) {
-            const int at = DMA ? ((((col >> 4) * Bp + row) << 4) + (col & 15)) : (row * S + col);
-            const u32x2 r = *as_lds(reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(xb) + at));
+            const u32x2 r = *as_lds(reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(xb) + row * S + col));
             return (f32x4){cvt16(r.x & 0xFFFFu, dt), cvt16(r.x >> 16, dt), cvt16(r.y & 0xFFFFu, dt), cvt16(r.y >> 16, dt)};
         } else {
             return *as_lds(reinterpret_cast<const f32x4*>(xb + row * S + col));
         }
     };
-    const uint32_t lds_base = (uint32_t)(uintptr_t)as_lds(lds);
-    const void* zeros = a.sync + (size_t)K * PERSIST_SYNC_STRIDE + 48;      // 64 bytes nobody writes during the launch (zeroed before it)
     auto stage = [&](const ResUnit& un, float* dst, int t) {     // rows of batch t -> LDS
         const int nv = (int)min((int64_t)a.B, a.N - (int64_t)t * a.B);
-        if constexpr (DMA) {
-            // lane -> (row, 16-byte half of the row's 32-byte k-block); this wave's k-blocks only
-            const int r = lane >> 1, half = lane & 1;
-            const int32_t* ord = cand_order(sa.order, sa.g, un.gidx);
-            int64_t row = -1;
-            if (r < nv) row = ord ? (int64_t)ord[a.pos0 + (int64_t)t * a.B + r] : (int64_t)t * a.B + r;
-            const uint32_t dst0 = lds_base + (uint32_t)((dst - lds) << 2);
-            if (r < Bp) {
-#pragma unroll
-                for (int sidx = 0; sidx < NTR; ++sidx) {
-                    const int kb = wave + STEP_NW * sidx;
-                    if (kb < un.nkb) {
-                        const void* src = row >= 0 ? static_cast<const void*>(reinterpret_cast<const uint16_t*>(un.tp) + row * un.width + un.k0 + kb * 16 + half * 8)
-                                                   : zeros;
-                        glds16(src, __builtin_amdgcn_readfirstlane(dst0 + (uint32_t)(kb * Bp * 32)));
-                    }
-                }
-            }
-        } else if constexpr (X16)
+        if constexpr (X16)
             stage_table16(reinterpret_cast<uint16_t*>(dst), un.S, un.tp, un.width, un.k0, un.cc, cand_order(sa.order, sa.g, un.gidx), a.pos0 + (int64_t)t * a.B, t * a.B, nv, Bp, tid, STEP_THREADS);
         else
             stage_table(dst, un.S, un.tp, sa.tab.dtype, un.width, un.k0, un.cc, cand_order(sa.order, sa.g, un.gidx), a.pos0 + (int64_t)t * a.B, t * a.B, nv, Bp, tid, STEP_THREADS);
@@ -291,7 +256,7 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
             for (int w = 1; w < STEP_NW; ++w)
                 sum += *reinterpret_cast<const f32x4*>(wred + ((w * MB + slot) << 8) + ln * 4);
             // (transposed slabs: lane ln holds batch row slot * 16 + (ln & 15); the chain does not read rows beyond the batch)
-            if (!MFAS_RES_TRANSPOSED_SLABS || slot * 16 + (ln & 15) < nv_next) stc4<true>(sa.stepbuf, un.part + (slot << 8) + ln * 4, sum);
+            if (slot * 16 + (ln & 15) < nv_next) stc4<true>(sa.stepbuf, un.part + (slot << 8) + ln * 4, sum);
         }
         // Only the MB waves that stored the slab wait for the stores' acknowledgements; the LAST of them to see its own arrive counts
         // the unit's arrival (an LDS ticket).  The other waves go on — the poller (wave 7) already looks for the workgroup's next
@@ -309,7 +274,6 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
     for (int u = 0; u < NU; ++u) {
         if (U[u].valid) {            // (wave-uniform, workgroup-uniform)
             stage(U[u], lds + res_xbo(U[u], 0), 0);
-            if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the LDS-DMA copy is invisible to the compiler's counters)
             __syncthreads();
             f32x4 yacc[MB];
 #pragma unroll
@@ -423,8 +387,6 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
                 float gsc = 1.0f;
                 if (sa.g.alphas) gsc = ldc1<true>(sa.stepbuf + un.gsco);
                 const float a_ss = a.scal[2 * (int64_t)(a.gstep0 + t)], a_bc2s = a.scal[2 * (int64_t)(a.gstep0 + t) + 1];
-                // this wave's own LDS-DMA copies (batch t+1, requested after the unit's previous step) have landed: nothing else reads them
-                if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 f32x4 yacc[MB];
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb) yacc[mb] = (f32x4){0.f, 0.f, 0.f, 0.f};

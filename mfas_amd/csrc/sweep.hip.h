@@ -390,65 +390,6 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& 
 }
 
 // ------------------------------------------------------------------------------------------------
-// sweep_multi_body — a FEATURE unit that spans `nsub` consecutive 64-column chunks of its segment (round 4; SegDesc::nsub > 1, only
-// with exactly 8 row blocks: wave = row block, R in 113..128).  The memory walk is that of the one-chunk units — chunk after chunk,
-// each a contiguous [rb][kb][256] block per plane — but dy is staged once, the wave's forward accumulator lives in registers
-// across the chunks, and the unit writes ONE partial slab: the slab traffic (8 KB written per chunk and read back by the chain)
-// and the dy staging shrink by the group factor.  Arithmetic per tile = tile_run's; only the k-summation of the forward partial
-// is regrouped (as with any other chunk size).  OPT-IN (MFAS_SUBCHUNKS=n): measured slower than one-chunk units on MI355X (2 / 4 / 8
-// chunks per unit: 314 / 320 / 327 us per launch against 299, profiles/r04_subchunks_preload_prio.log) although 4-7 % fewer bytes move —
-// the workgroup-wide barrier between chunks makes every wave wait for the slowest, where one-chunk workgroups hand their wave slots
-// to the next workgroup one wave at a time.
-// ------------------------------------------------------------------------------------------------
-template <int MB, bool NT, int U>
-__device__ __forceinline__ void sweep_multi_body(const SweepArgs& a, const SweepStep& st, const int bid, float* lds) {
-    const SegDesc& d = a.desc[bid];
-    const CandDev& cd = a.cands[d.cand];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l15 = lane & 15, lg = lane >> 4;
-    constexpr int Bp = MB * 16;
-    const int cc = d.cc, rows_p = d.rows_p, nkb = cc >> 4;
-    const int ST = cc + 16, SN = cc + 4, SD = rows_p + 16;
-    float* xt = lds;
-    float* xn = xt + Bp * ST;
-    float* dyl = xn + Bp * SN;
-    const bool upd = st.upd != 0;
-    const bool fwd = st.fwd != 0;
-    if (!upd && !fwd) return;
-    const int64_t sbo = cd.step_off;
-    const int nsub = d.nsub;
-    const void* tp = d.kind == KIND_S ? a.tab.s[d.tap] : a.tab.v[d.tap];
-    const int32_t* ord = cand_order(a.order, a.g, cd.gidx);
-    if (upd) stage_f32<false>(dyl, SD, a.stepbuf, sbo + a.g.sb_dy + (int64_t)d.cell * Bp * a.g.Rp, d.seg_nrb * 16, rows_p, Bp, tid, STEP_THREADS);
-    float gsc = 1.0f;
-    if (a.g.alphas && upd) gsc = a.stepbuf[sbo + a.g.sb_gsc + d.cell * 2 + d.kind];
-    const AdamC ac = adam_consts(a.ac, upd ? st.ss : 0.f, upd ? st.bc2s : 1.f);
-    f32x4 yacc[MB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb) yacc[mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int rb = wave;            // 8 row blocks, one per wave
-    for (int sub = 0; sub < nsub; ++sub) {
-        const int k0 = d.k0 + sub * cc;
-        float* Wp = a.plane + d.w_off + (int64_t)sub * rows_p * cc;
-        if (sub > 0) __syncthreads();                    // every wave is done with the previous chunk's rows
-        if (upd) stage_table(xt, ST, tp, a.tab.dtype, d.width, k0, cc, ord, st.pos_t, st.base_t, st.nvalid_t, Bp, tid, STEP_THREADS);
-        if (fwd) stage_table(xn, SN, tp, a.tab.dtype, d.width, k0, cc, ord, st.pos_n, st.base_n, st.nvalid_n, Bp, tid, STEP_THREADS);
-        __syncthreads();
-        float dyf[MB * 4];
-#pragma unroll
-        for (int j = 0; j < MB * 4; ++j) dyf[j] = upd ? dyl[(4 * j + lg) * SD + rb * 16 + l15] : 0.f;
-        tile_run<MB, NT, U, false>(Wp, Wp + a.plane_stride, Wp + 2 * a.plane_stride, rb, nkb, 0, 1, xt, ST, xn, SN, dyf, gsc, ac, upd, fwd, yacc,
-                                   nullptr, d.seg_nrb, lane, (a.g.B + 3) >> 2);
-    }
-    if (fwd) {
-        const int64_t part = sbo + a.g.sb_part + (((int64_t)(cd.part_cell_off[d.cell] + d.part_idx) * d.seg_nrb * MB) << 8);
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-            *reinterpret_cast<f32x4*>(a.stepbuf + part + ((rb * MB + mb) << 8) + lane * 4) = yacc[mb];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
 // sweep_tap_body — the same fused dW + Adam + next-step forward for SMALL R (1, 2 or 4 row blocks): a column chunk of
 // ONE feature tap is staged once and shared by up to 8/nrb segments (candidates x cells) that read this tap; every wave
 // owns one (segment, row block), streams its contiguous tiles and writes its forward partial directly — no cross-wave

@@ -37,10 +37,10 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().mfas_version() >= 100
 
 
-def test_empty_environment_selects_the_tested_defaults():
+def test_switches_default_when_unset_and_retired_ones_are_ignored():
     """The library's switches live in ONE struct parsed in ONE place (mfas_hip.hip::tuning_from_env, at create / plan time).  With no
     MFAS_* variable set the parsed set is exactly the defaults the suites run; every documented variable moves exactly its own
-    field; the product library never parses the test hooks; INTEGRATION.md's table names every switch (and nothing else in the
+    field; the product library never parses the test hooks nor the retired switches; INTEGRATION.md's table names every switch (and nothing else in the
     engine sources calls getenv, apart from the process-wide MFAS_NO_ROCTX marker switch)."""
     code = r"""
 import sys, os, json
@@ -56,17 +56,14 @@ print(json.dumps(_lib.tuning()))
         import json
         return json.loads(out.stdout.strip().splitlines()[-1])
 
-    defaults = {"persist": "-1", "no_lean_chain": "0", "persist_no_resident": "0", "persist_no_res_chain": "0", "subchunks": "0",
-                "subchunk_skip": "0", "groups": "0", "same_group": "-1", "no_tap_major": "0", "force_tap_major": "0", "no_red_in_sweep": "0", "force_red_in_sweep": "0",
+    defaults = {"persist": "-1", "no_lean_chain": "0", "groups": "0", "same_group": "-1", "no_tap_major": "0", "force_tap_major": "0", "no_red_in_sweep": "0",
                 "occ_bytes": "-1", "no_xcd_placement": "0", "n_xcd": "0", "persist_trace": "0", "nt": "-1", "eval_no_x16": "0",
                 "eval_no_msplit": "0", "eval_no_b3": "0", "eval_no_wl": "0", "no_gather": "0", "gather_verbose": "0", "no_plain_chain": "0",
                 "persist_verbose": "0", "prof_every": "16", "chain_split": "-1", "test_not_resident": "-1", "test_lose_step": "-1", "hooks": "0"}
     assert parsed() == defaults
-    env_of = {"persist": ("MFAS_PERSIST", "0", "0"), "no_lean_chain": ("MFAS_NO_LEAN_CHAIN", "1", "1"),
-              "persist_no_resident": ("MFAS_PERSIST_NO_RESIDENT", "1", "1"), "persist_no_res_chain": ("MFAS_PERSIST_NO_RES_CHAIN", "1", "1"),
-              "subchunks": ("MFAS_SUBCHUNKS", "4", "4"), "subchunk_skip": ("MFAS_SUBCHUNK_SKIP", "3", "3"), "groups": ("MFAS_GROUPS", "2", "2"),
+    env_of = {"persist": ("MFAS_PERSIST", "0", "0"), "no_lean_chain": ("MFAS_NO_LEAN_CHAIN", "1", "1"), "groups": ("MFAS_GROUPS", "2", "2"),
               "same_group": ("MFAS_SAME_GROUP", "2", "2"), "no_tap_major": ("MFAS_NO_TAP_MAJOR", "1", "1"),
-              "force_tap_major": ("MFAS_FORCE_TAP_MAJOR", "1", "1"), "no_red_in_sweep": ("MFAS_NO_RED_IN_SWEEP", "1", "1"), "force_red_in_sweep": ("MFAS_FORCE_RED_IN_SWEEP", "1", "1"),
+              "force_tap_major": ("MFAS_FORCE_TAP_MAJOR", "1", "1"), "no_red_in_sweep": ("MFAS_NO_RED_IN_SWEEP", "1", "1"),
               "occ_bytes": ("MFAS_OCC_BYTES", "3e8", "3e+08"), "no_xcd_placement": ("MFAS_NO_XCD_PLACEMENT", "1", "1"), "n_xcd": ("MFAS_XCDS", "4", "4"),
               "persist_trace": ("MFAS_PERSIST_TRACE", "1", "1"), "nt": ("MFAS_NT", "1", "1"), "eval_no_x16": ("MFAS_EVAL_NO_X16", "1", "1"),
               "eval_no_msplit": ("MFAS_EVAL_NO_MSPLIT", "1", "1"), "eval_no_b3": ("MFAS_EVAL_NO_B3", "1", "1"), "eval_no_wl": ("MFAS_EVAL_NO_WL", "1", "1"),
@@ -80,6 +77,10 @@ print(json.dumps(_lib.tuning()))
     # the product library does not parse the hooks
     hooked = parsed(MFAS_PERSIST_TEST_NOT_RESIDENT="1", MFAS_PERSIST_TEST_LOSE_STEP="3")
     assert hooked == defaults
+    # ... nor the switches of the retired variants (multi-chunk sweep units, forced reduce-in-sweep, the old MFAS_PERSIST=0 aliases)
+    retired = parsed(MFAS_SUBCHUNKS="4", MFAS_SUBCHUNK_SKIP="3", MFAS_FORCE_RED_IN_SWEEP="1", MFAS_PERSIST_NO_RESIDENT="1",
+                     MFAS_PERSIST_NO_RES_CHAIN="1")
+    assert retired == defaults
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for var, _, _ in env_of.values():
         assert var in doc, var
