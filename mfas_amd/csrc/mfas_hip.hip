@@ -681,8 +681,11 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
         const size_t lds_rchain = p->res_chain ? p->lds_chain + 16 + 4 * (size_t)(LeanLds<1>::own_floats() - LeanLds<1>::stage_floats()) : 0;
         p->lds_president = ((std::max(lds_rchain, lds_res) + 15) & ~(size_t)15) + 4 * PERSIST_LDS_WORDS;
     }
+    // dev-pass row blocks per wave: k_eval is built for 1, 2, 4 and 8 (eval.hip.h clamps / skips row blocks >= nrb), so 3 and
+    // 5..7 (R = 257..448) take the next build up
     p->nrbw = (g.nrb + 3) / 4;
     if (p->nrbw == 3) p->nrbw = 4;
+    else if (p->nrbw > 4 && p->nrbw < 8) p->nrbw = 8;
     for (p->mbe = 4; p->mbe >= 1; p->mbe >>= 1) {
         const int ME = p->mbe * 16;
         p->lds_eval = ((size_t)ME * std::max(EVAL_CE + 8, g.Cp + 4) + (size_t)ME * (g.Rp + 8)) * 4;   // strides: eval.hip.h
@@ -1178,8 +1181,8 @@ static int check_table(const mfas_population* p, const mfas_table* t, bool need_
     if (p->g.loss_mode == 0 && !t->label) return fail(MFAS_EINVAL, "table: labels missing");
     if (p->g.loss_mode == 1 && !t->multilabel) return fail(MFAS_EINVAL, "table: multi-hot targets missing (loss_mode 1)");
     if (t->dtype < 0 || t->dtype > 2) return fail(MFAS_EINVAL, "table: bad dtype");
-    for (int j = 0; j < 4; ++j)
-        if (!t->s[j] || !t->v[j]) return fail(MFAS_EINVAL, "table: null tap pointer");
+    for (int j = 0; j < MFAS_MAX_TAPS; ++j)      // (a width-0 tap is an unused slot: no configuration may select it, so no pointer is needed)
+        if ((!t->s[j] && p->g.sw[j] > 0) || (!t->v[j] && p->g.vw[j] > 0)) return fail(MFAS_EINVAL, "table: null tap pointer");
     if (need_logits && (!t->vlogit || !t->slogit)) return fail(MFAS_EINVAL, "multitask needs vlogit/slogit");
     return MFAS_OK;
 }

@@ -216,8 +216,8 @@ class FeatureTable:
 
     def to_c(self) -> _lib.mfas_table:
         t = _lib.mfas_table()
-        some = next(iter(self.taps.values())).data_ptr()
-        for j in range(_lib.MAX_TAPS):   # taps a population never selects may be absent: any valid pointer will do
+        some = next((v.data_ptr() for v in self.taps.values() if v.numel()), 0)
+        for j in range(_lib.MAX_TAPS):   # taps a population never selects may be absent: any valid pointer will do (width 0: none)
             t.s[j] = self.taps[f"s{j}"].data_ptr() if f"s{j}" in self.taps else some
             t.v[j] = self.taps[f"v{j}"].data_ptr() if f"v{j}" in self.taps else some
         t.vlogit = None if self.vlogit is None else self.vlogit.data_ptr()

@@ -8,7 +8,9 @@ import pytest
 
 torch = pytest.importorskip("torch")
 from oracle import np_oracle as O
+from tests import ref64 as R64
 from tests.helpers import engine_hyper, etas_for, oracle_steps, rel_err
+from tests.test_gpu_ref64 import TAU_LOGITS
 from tests.test_gpu_parity import check_state, mk_pop, table
 
 pytestmark = pytest.mark.gpu
@@ -61,6 +63,8 @@ def test_random_population_steps(case):
         feats = {key: v[row0:row0 + nrows] for key, v in t.items() if key != "label"}
         want, _ = O.forward(P, c, hp, feats, False)
         assert rel_err(logits.cpu().numpy(), want) < 2e-4, (case, k)
+        want64, M64, _ = R64.forward(P, c, hp, feats, False)          # and elementwise against the float64 reference
+        R64.assert_close64(logits.cpu().numpy(), want64, M64, TAU_LOGITS, f"fuzz case {case} cand {k} eval forward")
         pred = (want + feats["vlogit"] + feats["slogit"]).argmax(1) if hp.multitask else want.argmax(1)
         assert abs(corr - int((pred == t["label"][row0:row0 + nrows]).sum())) <= 1, (case, k)
     pop.close()

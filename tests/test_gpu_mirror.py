@@ -786,16 +786,27 @@ def test_bf16x3_eval_products_match_f32_products(dev, R, bn, alphas, K, mixed, w
                 pop.set_params(0, flat)
             stats, status = pop.train(ta, tb, E, etas, order=order)
             logits = [pop.forward(k, tb, row0=3, nrows=Nd - 5).cpu().numpy() for k in range(K)]
+            params = [{key: v.numpy() for key, v in pop.get_state_dict(k).items()} for k in range(K)]
             pop.close()
         finally:
             os.environ.pop("MFAS_EVAL_NO_B3", None)
         assert not status.any()
-        return stats, logits
+        return stats, logits, params
 
-    (s_new, l_new), (s_old, l_old) = run(False), run(True)
+    (s_new, l_new, p_new), (s_old, l_old, _) = run(False), run(True)
     assert s_new["train_loss_sum"].tobytes() == s_old["train_loss_sum"].tobytes()      # training does not depend on the dev pass
     assert np.abs(s_new["dev_corrects"] - s_old["dev_corrects"]).max() <= 1
     np.testing.assert_allclose(s_new["dev_loss_sum"], s_old["dev_loss_sum"], rtol=1e-6)
     for a, b in zip(l_new, l_old):
         assert np.abs(a - b).max() <= 2e-5 * max(1.0, np.abs(b).max())
+    # both builds against the float64 reference on the trained parameters, elementwise (tests/ref64.py): a B3 build that lost the
+    # low weight bits would still pass the max-scaled bound above
+    from tests import ref64 as R64
+    from tests.test_gpu_ref64 import TAU_LOGITS
+    dv = O.synth_table(Nd, 4, snr=0.6, **okw)
+    feats = {key: O.bf16_round(v)[3:Nd - 2] for key, v in dv.items() if key[0] in "sv"}
+    for k in range(K):
+        want, Mw, _ = R64.forward(p_new[k], confs[k], hp, feats, False)
+        R64.assert_close64(l_new[k], want, Mw, TAU_LOGITS, f"B3 build R{R} cand {k}")
+        R64.assert_close64(l_old[k], want, Mw, TAU_LOGITS, f"f32-product build R{R} cand {k}")
     assert (s_old["dev_corrects"] > 0).any()
