@@ -38,7 +38,7 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_switches_default_when_unset_and_retired_ones_are_ignored():
-    """The library's switches live in ONE struct parsed in ONE place (mfas_hip.hip::tuning_from_env, at create / plan time).  With no
+    """The library's switches live in ONE struct parsed in ONE place (plan.hip.h::tuning_from_env, at create / plan time).  With no
     MFAS_* variable set the parsed set is exactly the defaults the suites run; every documented variable moves exactly its own
     field; the product library never parses the test hooks nor the retired switches; INTEGRATION.md's table names every switch (and nothing else in the
     engine sources calls getenv, apart from the process-wide MFAS_NO_ROCTX marker switch)."""
