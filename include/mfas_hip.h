@@ -131,8 +131,9 @@ int mfas_population_init_torch_streams(mfas_population* pop, const uint64_t* see
  * for each epoch: train over `train` in the given sample order (order: device int32 [epochs][N_train],
  * NULL = sequential), then evaluate `dev`.  step_scalars: HOST float2 per train step
  * {lr_t/(1-beta1^t), sqrt(1-beta2^t)} (scheduler.py:25-46 + torch Adam bias corrections).
- * max_steps >= 0 stops after that many train steps of the first epoch (debug/known-answer tests;
- * dev evaluation is skipped).  stats: HOST [K][epochs].  status: HOST [K], 1 = non-finite loss seen.
+ * max_steps >= 0 stops after that many train steps in all, counted across epochs (an epoch that starts is cut short; later
+ * epochs do not run; debug/known-answer tests; dev evaluation is skipped).  stats: HOST [K][epochs].  status: HOST [K], 1 =
+ * non-finite loss seen.
  * snapshot_best != 0 keeps the best-dev-epoch parameters and restores them at the end (:82-86).
  * Every call starts from zeroed Adam moments and step count (a freshly constructed optimizer). */
 int mfas_population_train(mfas_population* pop, const mfas_table* train, const mfas_table* dev,

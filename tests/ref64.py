@@ -112,11 +112,13 @@ def forward(params, conf, hp: "O.Hyper", feats, train: bool, seed: int = 0, step
     return logits, Ml, {"cells": cells, "conf": conf, "out": out, "M_out": M_out, "Wc": Wc}
 
 
-def backward(params, hp: "O.Hyper", cache, dlogits):
-    """Gradients of every central parameter for an arbitrary dL/dlogits.  Returns (grads, M_grads) keyed like the state dict."""
+def backward(params, hp: "O.Hyper", cache, dlogits, M_dlogits=None):
+    """Gradients of every central parameter for an arbitrary dL/dlogits.  Returns (grads, M_grads) keyed like the state dict.
+    M_dlogits: the magnitude of dlogits' own error (a loss gradient formed from computed logits, ce_dlogits / bce_dlogits); it
+    joins |dlogits| wherever that multiplies a forward quantity, which is sound because M_out >= |out| in every such product."""
     conf = cache["conf"]
     dl = _f(dlogits)
-    adl = np.abs(dl)
+    adl = np.abs(dl) if M_dlogits is None else np.abs(dl) + _f(M_dlogits)
     G, M = {}, {}
     G["central_classifier.weight"] = dl.T @ cache["out"]
     M["central_classifier.weight"] = adl.T @ cache["M_out"]
@@ -301,3 +303,126 @@ def assert_close64(got, ref, M, tau: float, tag: str, record: Optional[str] = No
         raise AssertionError(f"{tag}: worst |got - ref64| = {r:.3g} * 2^-24 * M > tau = {tau:g} at element {tuple(int(i) for i in idx)}"
                              f" (got {g!r}, ref64 {f!r}, M {m:.4g})")
     return r
+
+
+# ------------------------------------------------------------------------------------------------ one train step
+# train() is pinned one step at a time: ref64 starts from the float32 state the engine (or the float32 oracle) itself held
+# before the step, taken as exact inputs, so nothing Adam's sign-like first steps amplify is ever compared.
+UNDERFLOW = 2.0 ** -126     # a float32 result below the smallest normal is rounded at 2^-149 absolute, or flushed to 0
+
+
+def ce_dlogits(logits, Ml, labels, n, tau_logits):
+    """dL/dlogits of the mean cross entropy over n rows, d = (softmax - onehot) / n, and its magnitude M_dl.
+    A logit error |delta_i| <= tau_logits 2^-24 Ml_i moves s_j by at most s_j (|delta_j| + sum_i s_i |delta_i|); the argument of
+    exp, x_j - max, is itself rounded at 2^-24 |x_j - max| (the same form, two roundings when it is scaled for exp2); exp, the
+    row sum, the two divisions and the subtraction of the one-hot each round s_j or d_j once more."""
+    lg, Ml = _f(logits), _f(Ml)
+    mx = lg.max(1, keepdims=True)
+    e = np.exp(lg - mx)
+    s = e / e.sum(1, keepdims=True)
+    d = s.copy()
+    d[np.arange(len(lg)), labels] -= 1.0
+    d /= n
+    ax = np.abs(lg - mx)
+    M = (tau_logits * s * (Ml + (s * Ml).sum(1, keepdims=True)) + 2.0 * s * (ax + (s * ax).sum(1, keepdims=True)) + 4.0 * s) / n \
+        + 4.0 * np.abs(d)
+    return d, M
+
+
+def bce_dlogits(logits, Ml, z, w, n, C, tau_logits):
+    """dL/dlogits of the weighted BCE-with-logits averaged over n rows and C classes, d = (-w z (1 - s) + (1 - z) s) / (n C),
+    s = sigmoid(x), and its magnitude: the logit sensitivity s (1 - s) (w z + 1 - z) / (n C); s rounds a few times relative to
+    itself, (1 - s) of a float32 s is exact only to 2^-24 absolute; the sum and the division round d itself."""
+    lg, Ml, z, w = _f(logits), _f(Ml), _f(z), _f(w)
+    s = _sig(lg)
+    k = (w * z + (1.0 - z)) / (n * C)
+    d = (-w * z * (1.0 - s) + (1.0 - z) * s) / (n * C)
+    M = tau_logits * s * (1.0 - s) * k * Ml + 4.0 * k * (s + z * (1.0 - s)) + 4.0 * np.abs(d)
+    return d, M
+
+
+def adam_step64(w, m, v, g, Mg, scalars, hp: "O.Hyper", tau_v=1.0, m_new=None, v_new=None):
+    """One Adam step with L2 weight decay (torch.optim.Adam, oracle/np_oracle.py adam_step) in float64 from the float32 state
+    (w, m, v) and the float64 gradient g with magnitude Mg; scalars = (step size lr / (1 - beta1^t), sqrt(1 - beta2^t)).
+    Returns ((m', M_m), (v', M_v), (w', M_w)):
+      m' = m + (1 - b1) (g' - m), g' = g + wd w,   M_m carried through the same graph on absolute values;
+      v' = b2 v + (1 - b2) g'^2.  With delta = tau_v 2^-24 M_g' the error of g', the allowance is (1 - b2)(2 |g'| delta + delta^2)
+           plus the recurrence's own roundings (the float32 constants b2 and 1 - b2, then b2 v, (1 - b2) g', . g' and the sum:
+           six of at most 2^-24 |v'| each, taken twice — where g' is tiny three of them act alone on all of v', and the rule
+           must keep its x4 margin there) and the
+           underflow floor; M_v is that allowance / 2^-24 (compare with tau 1);
+      w' = w - ss m'/(sqrt(v')/bc2s + eps) evaluated on m_new / v_new when given (the float32 moments the implementation itself
+           wrote: a pure elementwise function of them, so no cancellation enters), M_w = |w| + |dw|.
+    Every allowance carries the underflow floor 2^-126 (absolute): a weight may be subnormal (wd w then underflows)."""
+    w, m, v, g, Mg = _f(w), _f(m), _f(v), _f(g), _f(Mg)
+    ss, bc2s = float(scalars[0]), float(scalars[1])
+    b1, b2, wd = hp.beta1, hp.beta2, hp.wd
+    g1 = g + wd * w
+    Mg1 = Mg + wd * np.abs(w) + np.abs(g1)
+    m1 = m + (1.0 - b1) * (g1 - m)
+    Mm = np.abs(m) + (1.0 - b1) * (Mg1 + np.abs(m)) + np.abs(m1) + UNDERFLOW / U
+    v1 = b2 * v + (1.0 - b2) * g1 * g1
+    delta = tau_v * U * Mg1
+    Mv = ((1.0 - b2) * (2.0 * np.abs(g1) * delta + delta * delta) + UNDERFLOW) / U + 12.0 * np.abs(v1)
+    mm = m1 if m_new is None else _f(m_new)
+    vv = v1 if v_new is None else _f(v_new)
+    dw = ss * mm / (np.sqrt(vv) / bc2s + hp.adam_eps)
+    return (m1, Mm), (v1, Mv), (w - dw, np.abs(w) + np.abs(dw) + UNDERFLOW / U)
+
+
+def train_step64(state, conf, hp: "O.Hyper", batch, seed, step, eta, t, tau_logits, tau_v, observed=None, pos_weight=None):
+    """One train step of one candidate in float64.  state = {"w": state dict (parameters and BN running statistics), "m": ..,
+    "v": ..} is the float32 state before the step; batch holds the rows of this step in batch order (taps, label, and vlogit /
+    slogit / multilabel where the head uses them): its length is the step's nvalid.  seed / step select the dropout masks (step =
+    the global 0-based step), eta is this step's learning rate and t the 1-based Adam step.  observed = {"m": .., "v": ..}: the
+    moments the implementation wrote, on which the expected parameters are evaluated.
+    Returns {"m" / "v" / "w" / "runstat": {key: (expected, M)}, "loss": (sum over the rows, bound), "count": (lo, hi)}."""
+    P = state["w"]
+    n = len(batch["label"])
+    feats = {k: a for k, a in batch.items() if k not in ("label", "multilabel")}
+    lg, Ml, cache = forward(P, conf, hp, feats, True, seed=seed, step=step)
+    if hp.loss_mode == 1:
+        pw = np.ones(hp.C) if pos_weight is None else _f(pos_weight)
+        dl, Mdl = bce_dlogits(lg, Ml, batch["multilabel"], pw, n, hp.C, tau_logits)
+    else:
+        dl, Mdl = ce_dlogits(lg, Ml, batch["label"], n, tau_logits)
+    G, MG = backward(P, hp, cache, dl, M_dlogits=Mdl)
+    out = {"m": {}, "v": {}, "w": {}}
+    sc = O.adam_scalars(float(eta), int(t), hp)
+    for key in O.trainable_keys(conf, hp):
+        om = None if observed is None else observed["m"][key]
+        ov = None if observed is None else observed["v"][key]
+        em, ev, ew = adam_step64(P[key], state["m"][key], state["v"][key], G[key], MG[key], sc, hp, tau_v=tau_v, m_new=om, v_new=ov)
+        out["m"][key], out["v"][key], out["w"][key] = em, ev, ew
+    rs, Mrs = running_stats(P, hp, cache) if hp.bn else ({}, {})
+    out["runstat"] = {k: (rs[k], Mrs[k]) for k in rs}
+    loss, lb, lo, hi = dev_stats(lg, Ml, hp, tau_logits, labels=batch["label"], vlogit=feats.get("vlogit"), slogit=feats.get("slogit"),
+                                 z=batch.get("multilabel"), pos_weight=pos_weight)
+    out["loss"], out["count"] = (loss, lb), (lo, hi)
+    return out
+
+
+def check_train_step(exp, got, loss, count, taus, tag, rec=None, hard=True):
+    """One observed step against train_step64's expectation.  got = {"w" / "m" / "v": state dict after the step} (running
+    statistics in "w"); taus = {"m", "v", "w", "runstat", "loss"}.  Returns the worst ratio per quantity ("loss": the fraction of
+    its bound, "count": 0 inside [lo, hi], else inf; count None: the head keeps no train count); hard: raise on the first quantity over its tau, naming the element.  rec: the
+    suffix under which RATIOS records them (train_m/<rec> ...)."""
+    worst = {}
+    for q, src in (("m", "m"), ("v", "v"), ("w", "w"), ("runstat", "w")):
+        r = 0.0
+        for key, (ref, M) in exp[q].items():
+            if hard:
+                r = max(r, assert_close64(got[src][key], ref, M, taus[q], f"{tag} {q} {key}", record=f"train_{q}/{rec}" if rec else None))
+            else:
+                r = max(r, worst_ratio(got[src][key], ref, M)[0])
+        worst[q] = r
+    ref_loss, lb = exp["loss"]
+    worst["loss"] = abs(float(loss) - ref_loss) / max(lb, 1e-300)
+    lo, hi = exp["count"]
+    worst["count"] = 0.0 if count is None or lo <= int(count) <= hi else float("inf")
+    if rec:
+        RATIOS[f"train_loss/{rec}"] = max(RATIOS.get(f"train_loss/{rec}", 0.0), worst["loss"])
+    if hard:
+        assert worst["loss"] <= taus["loss"], f"{tag} train_loss_sum: got {float(loss)!r}, ref64 {ref_loss!r}, bound {lb:.3g}"
+        assert count is None or lo <= int(count) <= hi, f"{tag} train_corrects: got {int(count)}, ref64 allows [{lo}, {hi}]"
+    return worst

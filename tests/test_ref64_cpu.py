@@ -252,3 +252,146 @@ def test_mutation_bn_biased_running_variance():
         k = f"fusion_layers.{i}.2.running_var"
         biased = (p[k] + F32(hp.bn_momentum) * (c["var"] - p[k])).astype(F32)
         _fails(biased, rs[k], Mrs[k], G.TAU_RUNSTAT)
+
+
+# ------------------------------------------------------------------------------------------------ one train step (tests/test_gpu_train_ref64.py)
+# Calibration and power of the stepwise train() check, on the shapes, orders and learning rates the GPU test uses: the float32
+# oracle takes the engine's place, teacher-forced from its own state through ref64.train_step64.
+from tests import test_gpu_train_ref64 as GT  # noqa: E402
+
+
+class _PadMean(np.ndarray):
+    """Activations whose batch mean also counts one padded row (mutation 'bn_pad'); results of arithmetic on them are plain."""
+    _extra = None
+
+    def mean(self, axis=None, dtype=None, **kw):
+        m = np.asarray(self).mean(axis=axis, dtype=dtype, **kw)
+        return m if self._extra is None else (m + self._extra).astype(F32)
+
+
+def oracle_step32(st, conf, hp, batch, seed, step, eta, t, pw=None, mut="", stale=None):
+    """One train step of the float32 oracle from state st = {"w", "m", "v"}; returns (state after, loss sum, count or None).
+    mut names a deliberate error; stale: the parameters forward and backward read instead of st's (the running statistics and the
+    update stay on st's)."""
+    P = {k: v.copy() for k, v in st["w"].items()}
+    Pf = P if stale is None else {k: v.copy() for k, v in stale.items()}
+    n = len(batch["label"])
+    feats = {k: v for k, v in batch.items() if k not in ("label", "multilabel")}
+    orig_act = O._act
+    if mut == "bn_pad":     # a row beyond nvalid (zero inputs: its activation is act(bias)) counted in the batch mean
+        cell = [0]
+
+        def act(y, nl):
+            a = orig_act(y, nl).view(_PadMean)
+            a._extra = orig_act(P[f"fusion_layers.{cell[0]}.0.bias"], nl) / F32(len(y))
+            cell[0] += 1
+            return a
+        O._act = act
+    try:
+        logits, cache = O.forward(Pf, conf, hp, feats, True, seed=seed, step=step)
+    finally:
+        O._act = orig_act
+    if hp.loss_mode == 1:
+        loss, dlog = O.bce_loss(logits, batch["multilabel"], pw)
+        if mut == "no_pos_weight":
+            dlog = O.bce_loss(logits, batch["multilabel"], np.ones(hp.C, F32))[1]
+        count = None
+    else:
+        loss, dlog, preds = O.ce_loss(logits, batch["label"])
+        if hp.multitask:
+            preds = O.predict(logits + feats["vlogit"] + feats["slogit"])
+            loss = (loss + O.ce_loss(feats["vlogit"], batch["label"])[0]) + O.ce_loss(feats["slogit"], batch["label"])[0]
+        count = int((preds == batch["label"]).sum())
+    if mut == "div_B":
+        dlog = (dlog * F32(n) / F32(hp.B)).astype(F32)
+    grads = O.backward(Pf, hp, cache, dlog)
+    O.bn_update_running(P, hp, cache)
+    ad = O.AdamState(m={k: v.copy() for k, v in st["m"].items()}, v={k: v.copy() for k, v in st["v"].items()}, t=t - 1)
+    hq = hp
+    if mut == "no_wd":
+        import dataclasses
+        hq = dataclasses.replace(hp, wd=0.0)
+    if mut == "m_no_decay":
+        ad.m = {k: np.zeros_like(v) for k, v in ad.m.items()}
+    O.adam_step(P, grads, ad, float(eta), hq, O.trainable_keys(conf, hp))
+    return {"w": P, "m": ad.m, "v": ad.v}, float(loss) * n, count
+
+
+def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False):
+    """Steps 1..3 as test_gpu_train_ref64 sets them up, the float32 oracle checked step by step: worst ratio per quantity."""
+    hp = G.case_hyper(case)
+    seed = GT.SEED0 + G.CASE_IDS.index(case[0]) if seed is None else seed
+    conf, p0 = G.case_params(case, hp, seed)
+    N = hp.B + GT.ragged_rows(hp.B)
+    t = G.case_table(case, hp, N, seed, dtype)
+    order = GT.make_order(N, seed)
+    wrong = GT.make_order(N, seed, 2)[1]            # another candidate's order
+    etas = GT.step_etas(N, hp.B)
+    pw = G.pos_weight(hp) if hp.loss_mode == 1 else None
+    keys = O.trainable_keys(conf, hp)
+    hist = [{"w": p0, "m": {k: np.zeros_like(p0[k]) for k in keys}, "v": {k: np.zeros_like(p0[k]) for k in keys}}]
+    worst = {}
+    nb = -(-N // hp.B)
+    for j in range(1, GT.STEPS + 1):
+        batch, ep = GT.batch_of(t, order, hp.B, j)
+        seen, eta_j, t_j, m, stale = batch, etas[j - 1], j, mut, None
+        if mut == "div_B" and len(batch["label"]) == hp.B:
+            m = ""                                  # (only the ragged batch divides by something else than B)
+        if mut == "bn_pad" and len(batch["label"]) == hp.B:
+            m = ""
+        if mut == "scalars_prev" and j >= 2:
+            eta_j, t_j = etas[j - 2], j - 1
+        if mut == "stale_forward" and j >= 2:
+            stale = hist[j - 2]["w"]
+        if mut == "order_epoch0" and ep >= 1:
+            seen = GT.batch_of(t, order, hp.B, j - ep * nb)[0]
+        if mut == "order_other_candidate":
+            seen = GT.batch_of(t, wrong, hp.B, j)[0]
+        new, loss, count = oracle_step32(hist[-1], conf, hp, seen, seed, j - 1, eta_j, t_j, pw, m, stale)
+        exp = R64.train_step64(hist[-1], conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, GT.TAU_V, observed=new, pos_weight=pw)
+        r = R64.check_train_step(exp, new, loss, count, GT.TAUS, f"{case[0]} step {j}", hard=False)
+        worst = {q: max(worst.get(q, 0.0), r[q]) for q in r}
+        hist.append(new)
+    return worst
+
+
+def test_train_case_dtypes_rotate():
+    per = [sum(GT.case_dtype(c) == d for c in G.CASE_IDS) for d in G.DTYPES]
+    assert min(per) >= 10, per
+    assert GT.TAU_M == G.TAU_GRAD and GT.TAUS["runstat"] == G.TAU_RUNSTAT
+    assert all(2 <= GT.ragged_rows(B) < B for B in (3, 16, 17, 20, 32, 33, 64)) and GT.ragged_rows(2) == 2
+
+
+@pytest.mark.parametrize("case", G.CASES, ids=G.CASE_IDS)
+def test_train_step_calibration_margin(case):
+    """The float32 oracle stays under a quarter of each tau on the GPU test's own shapes, orders and steps."""
+    r = oracle_train_steps(case, GT.case_dtype(case[0]))
+    for q, tau in GT.TAUS.items():
+        assert r[q] * 4.0 <= tau, (case[0], q, r[q], tau)
+    assert r["count"] == 0.0, case[0]
+
+
+MUT_CE = ("mut", 32, 17, 20, G.W_A, [[3, 3, 0], [1, 2, 1]], True, 0.5, "")
+MUT_LM1 = ("mut", 17, 23, 16, G.W_A, [[0, 3, 0], [1, 1, 2]], False, 0.5, "lm1")
+MUTATIONS = {
+    "div_B": MUT_CE,                    # the loss gradient of the ragged batch divided by B instead of nvalid
+    "no_wd": MUT_CE,                    # weight decay left out of g'
+    "m_no_decay": MUT_CE,               # m = (1 - beta1) g' without - m_{j-1}
+    "scalars_prev": MUT_CE,             # the step scalars of step j - 1 used at step j
+    "stale_forward": MUT_CE,            # batch j run with w_{j-2}
+    "order_epoch0": MUT_CE,             # epoch 0's order row reused in epoch 1
+    "order_other_candidate": MUT_CE,    # rows gathered by another candidate's order
+    "bn_pad": MUT_CE,                   # a padded row counted in the BN batch mean
+    "no_pos_weight": MUT_LM1,           # pos_weight ignored in the BCE gradient
+}
+
+
+@pytest.mark.parametrize("mut", list(MUTATIONS))
+def test_train_step_mutations(mut):
+    """Each way a train step goes wrong exceeds its tau on at least one checked quantity; the same setup unmutated keeps x4."""
+    case = MUTATIONS[mut]
+    ok = oracle_train_steps(case, "bfloat16", seed=9)
+    assert all(ok[q] * 4.0 <= tau for q, tau in GT.TAUS.items()) and ok["count"] == 0.0, ok
+    bad = oracle_train_steps(case, "bfloat16", mut=mut, seed=9)
+    over = {q: bad[q] for q, tau in GT.TAUS.items() if bad[q] > tau}
+    assert over, (mut, bad)
