@@ -176,7 +176,9 @@ int mfas_population_set_profiling(mfas_population* pop, int32_t on);
 /* (new) The step schedule this population was laid out for, so that a measurement can name the kernel it
  * timed: info[0] = 1 persistent step loop (k_president: resident units + resident chain, one launch per epoch) / 0 launch per phase (k_step / k_chain);
  * info[1] = feature units resident in registers; info[2] = their workgroups; info[3] = units per resident workgroup;
- * info[4] = 1 when the resident lean chain owns OUT/HEAD; info[5] = bit 0: lean chain (R <= 16), bits 8..15: compute units one
+ * info[4] = 1 when the resident lean chain owns OUT/HEAD; info[5] = bit 0: lean chain (R <= 16), bit 1: the WIDE path (k_chain_wide +
+ * k_sweep_wide, launch per phase, the batch walked in tiles: batchsize > 64, more classes than the batch-resident softmax takes, or a
+ * step beyond the LDS; info[0] = 0 and info[6] = 1 then), bits 8..15: compute units one
  * candidate's general chain runs on in the same-group launch (round 6, chain_split; 1 otherwise); info[6] = candidate groups of the
  * launch-per-phase schedule (2 = fused A/B launches, 1 = chain and sweep back to back, -1 = one launch per step holding the chain
  * AND the sweep of the same candidates, released cell by cell through per-cell flags); info[7] = candidates. */
@@ -188,7 +190,8 @@ int mfas_population_schedule(const mfas_population* pop, int32_t info[8]);
  * resident ROUNDS with it (a share of a train_sampled_models call — /root/reference/models/search/ntu_searchable.py:38-94 trains
  * the configurations one after the other — that is too large for one resident population is trained as several).
  * info[0] = 1 resident persistent schedule / 0 launch per phase; info[1] = resident feature units; info[2] = their workgroups;
- * info[3] = units per resident workgroup; info[4] = feature-column chunk; info[5] = 1 lean chain (R <= 16, C <= 64, B <= 32);
+ * info[3] = units per resident workgroup; info[4] = feature-column chunk; info[5] = bit 0: lean chain (R <= 16, C <= 64, B <= 32),
+ * bit 1: the wide path (no resident form at any K);
  * info[6] = compute units of the device; info[7] = K. */
 int mfas_population_plan(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, int32_t K, int32_t device,
                          int32_t chunk_cols, int32_t info[8]);

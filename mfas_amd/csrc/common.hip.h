@@ -49,7 +49,8 @@ struct SegDesc {          // one workgroup of k_sweep / k_pack
     float init_bound;
     int32_t rb0, seg_nrb; // row-split units: first row block of this unit inside the segment, row blocks of the whole segment
                           // (rows_p = rows of THIS unit; w_off already points at row block rb0 of the chunk)
-    int32_t _pad2, _pad3; // (unused: keeps the struct, and every kernel's descriptor indexing, at 104 bytes)
+    int32_t sub_kb0, sub_nkb; // wide units (wide.hip.h): first k-block of the unit inside this layout chunk, its k-blocks (<= 8); 0 elsewhere
+                          // (the struct, and every kernel's descriptor indexing, stays at 104 bytes)
 };
 static_assert(sizeof(SegDesc) == 104, "SegDesc layout");
 

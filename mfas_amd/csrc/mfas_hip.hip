@@ -16,6 +16,7 @@
 //            algorithmic minimum with state in HBM.
 // Source layout (ONE translation unit; this file includes the rest): common.hip.h (device records, helpers, LDS
 // staging), sweep.hip.h (tile_run, sweep_body, sweep_tap_body), chain.hip.h (chain_body, chain_lean, softmax / BCE rows),
+// wide.hip.h (k_chain_wide / k_sweep_wide: the batch walked in tiles, for batch sizes and widths the others cannot hold),
 // eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe), plan.hip.h (host only: the switches, validate_inputs and
 // plan_layout — layout, schedule, LDS budgets and work lists decided before anything is allocated); below: k_step / k_chain, the kernel
 // tables (one function per kernel family: the only place an instantiation is named) and the host C ABI.
@@ -104,6 +105,7 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
     else chain_body<MB, true>(a, chain_step_of(a), (int)blockIdx.x, lds);
 }
 
+#include "wide.hip.h"
 #include "persist.hip.h"
 #include "eval.hip.h"
 #include "pack.hip.h"
@@ -232,6 +234,10 @@ static ChainKernel chain_kernel(int MB, bool lean) {
     return nullptr;
 }
 
+// the wide path (wide.hip.h): one chain build, the sweep with cached / nontemporal W/m/v streaming
+static ChainKernel wide_chain_kernel() { return k_chain_wide; }
+static StepKernel wide_sweep_kernel(bool nt) { return !nt ? k_sweep_wide<false> : k_sweep_wide<true>; }
+
 // one instantiation per unit form: f32 staging (one or two units per workgroup), 16-bit staging (the same, or one WIDE unit of up to
 // 1024 columns); plain: the chain compiled for the search default (1), for `--batchnorm` alone (2), or the general one (0)
 static PresidentKernel president_kernel(int MB, bool x16, bool wide, int nu, int plain) {
@@ -254,6 +260,11 @@ static void launch(void (*kernel)(A...), unsigned grid, size_t lds, hipStream_t 
 static hipError_t set_lds_all(const LayoutPlan& pl) {
     hipError_t e = hipSuccess;
     auto set = [&e](auto kernel, size_t bytes) { if (kernel && e == hipSuccess) e = set_lds(kernel, bytes); };
+    if (pl.wide) {
+        set(wide_chain_kernel(), pl.lds_chain);
+        for (int b = 0; b < 2; ++b) set(wide_sweep_kernel(b), pl.lds_step);
+        return e;
+    }
     for (int MB : {1, 2, 4})
         for (int b = 0; b < 2; ++b) {      // b: nontemporal (k_step*), lean (k_chain), 16-bit staging (k_president)
             for (int wpe : {2, 4}) { set(step_kernel(MB, b, wpe, false, 1), pl.lds_step); set(step_kernel(MB, b, wpe, true, 1), pl.lds_step); }
@@ -372,7 +383,7 @@ extern "C" int mfas_population_plan(const mfas_hyper* hp, const int32_t* confs, 
     LayoutPlan pl;
     if (int prc = plan_layout(hp, confs, n_cells, nullptr, K, chunk_cols, ncu, true, tuning_from_env(), pl)) return prc;
     info[0] = pl.persist ? 1 : 0; info[1] = pl.nres; info[2] = pl.nres_wg; info[3] = pl.res_nu;
-    info[4] = pl.chunk; info[5] = pl.lean_chain ? 1 : 0; info[6] = ncu; info[7] = K;
+    info[4] = pl.chunk; info[5] = (pl.lean_chain ? 1 : 0) | (pl.wide ? 2 : 0); info[6] = ncu; info[7] = K;
     return MFAS_OK;
 }
 
@@ -817,13 +828,17 @@ static void step(TrainCall& c, int gs, int upd, int fwd, int64_t ep, int64_t ts,
     }
     st.nchain = (int)nch;
     if (gs < 0) { st.sa.ntap = 0; }
-    if (nsw == 0) {   // chain only: the latency-tuned standalone kernel
-        launch(chain_kernel(MB, pl.lean_chain), nch, pl.lds_chain, p->stream, st.ca);
+    if (nsw == 0) {   // chain only: the latency-tuned standalone kernel (wide populations: theirs)
+        launch(pl.wide ? wide_chain_kernel() : chain_kernel(MB, pl.lean_chain), nch, pl.lds_chain, p->stream, st.ca);
         return;
     }
     // algorithmic HBM bytes of this group's update+forward sweep: 24 B/param + the batch's taps + labels
     ProfBracket prof(c, p->profiling && gs >= 0 && upd && fwd && ((c.nlaunch++ % p->prof_every) == 0),
                      pl.groups[gs].alg_state + pl.groups[gs].alg_feat * c.elt() + 8.0 * B * pl.groups[gs].nc);
+    if (pl.wide) {    // launch per phase only: the sweep of the one group, after its chain's launch
+        launch(wide_sweep_kernel(pl.nontemporal), nsw, pl.lds_step, p->stream, st);
+        return;
+    }
     const bool same = pl.same_group && gc == gs && upd;      // chain(g, t) and sweep(g, t) in ONE launch, per-cell flags
     const bool split = pl.chain_split && nch > 0;            // the chain blocks are chain_split parts (two-group launch: no flags, the kernel boundary)
     if (split) {      // NS parts per candidate, chain blocks = NS * ceil8(candidates)
@@ -1170,18 +1185,20 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
     memset(&st, 0, sizeof(st));
     st.sa.cands = p->d_cands; st.sa.plane = p->plane; st.sa.plane_stride = p->plan.plane_stride; st.sa.wt = p->wt;
     st.sa.stepbuf = p->stepbuf; st.sa.tab = *tab; st.sa.order = nullptr; st.sa.g = g; st.sa.g.order_stride = 0;
-    st.sa.desc = p->d_descs + p->plan.desc_start[k]; st.sa.tdesc = nullptr; st.sa.ntap = 0;
+    st.sa.desc = p->plan.wide ? p->groups[0].d_descs + p->plan.wide_start[k] : p->d_descs + p->plan.desc_start[k];
+    st.sa.tdesc = nullptr; st.sa.ntap = 0;
     st.sa.do_update = 0; st.sa.do_forward = 1;
     st.sa.pos_n = row0; st.sa.base_n = (int)row0; st.sa.nvalid_n = nrows;
     st.sa.pos_t = row0; st.sa.base_t = (int)row0; st.sa.nvalid_t = nrows;
     st.sa.ac = ac;
     st.nchain = 0;
-    const unsigned nsw = (unsigned)(p->plan.desc_start[k + 1] - p->plan.desc_start[k]);
     const LayoutPlan& pl = p->plan;
+    const unsigned nsw = pl.wide ? (unsigned)(pl.wide_start[k + 1] - pl.wide_start[k]) : (unsigned)(pl.desc_start[k + 1] - pl.desc_start[k]);
     size_t lds_need = pl.lds_step;   // (a population laid out for resident units budgets its streaming LDS without them)
-    for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) lds_need = std::max(lds_need, sweep_unit_lds(g, pl.descs[j]));
+    if (!pl.wide)
+        for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) lds_need = std::max(lds_need, sweep_unit_lds(g, pl.descs[j]));
     if (lds_need > 150 * 1024) return fail(MFAS_EINVAL, "train-mode forward: this population's units are too wide for the streaming kernels");
-    const StepKernel sweep_k = step_kernel(g.MB, false, g.MB == 1 ? 4 : 2, false, 1);
+    const StepKernel sweep_k = pl.wide ? wide_sweep_kernel(false) : step_kernel(g.MB, false, g.MB == 1 ? 4 : 2, false, 1);
     if (lds_need > pl.lds_step) HIPCHK(set_lds(sweep_k, lds_need));
     auto sweep = [&]() { launch(sweep_k, nsw, lds_need, p->stream, st); };
     if (dlogits) {
@@ -1201,7 +1218,7 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
     c.gstep = step_index; c.epoch = 0; c.E = 1; c.g = st.sa.g; c.stats = nullptr; c.status = p->d_status;
     c.yf_in_lds = p->plan.yf_in_lds ? 1 : 0; c.vec_in_lds = p->plan.vec_in_lds ? 1 : 0; c.pos_w = p->d_posw;
     c.yf_reduced = 0; c.logits_out = dlogits ? nullptr : logits; c.dlogits_in = dlogits; c.ac = ac;
-    launch(chain_kernel(g.MB, pl.lean_chain), 1u, pl.lds_chain, p->stream, st.ca);
+    launch(pl.wide ? wide_chain_kernel() : chain_kernel(g.MB, pl.lean_chain), 1u, pl.lds_chain, p->stream, st.ca);
     if (dlogits) {   // 3. dW of every matrix into its m slot (see the header comment); W, v-scaled-by-lr-0 steps leave W as it was
         st.sa.do_update = 1; st.sa.do_forward = 0;
         sweep();
@@ -1282,7 +1299,7 @@ extern "C" int mfas_population_schedule(const mfas_population* p, int32_t info[8
     if (!p || !info) return fail(MFAS_EINVAL, "null");
     const LayoutPlan& pl = p->plan;
     info[0] = pl.persist ? 1 : 0; info[1] = pl.nres; info[2] = pl.nres_wg; info[3] = pl.res_nu;
-    info[4] = pl.res_chain ? 1 : 0; info[5] = (pl.lean_chain ? 1 : 0) | (std::max(1, pl.chain_split) << 8); info[6] = pl.same_group ? -1 : (int32_t)pl.groups.size(); info[7] = p->K;
+    info[4] = pl.res_chain ? 1 : 0; info[5] = (pl.lean_chain ? 1 : 0) | (pl.wide ? 2 : 0) | (std::max(1, pl.chain_split) << 8); info[6] = pl.same_group ? -1 : (int32_t)pl.groups.size(); info[7] = p->K;
     return MFAS_OK;
 }
 

@@ -111,11 +111,7 @@ static int pick_chunk(int cols_p, int target) {
 static int validate_inputs(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, int32_t K) {
     if (!hp || !confs || !n_cells || K <= 0) return fail(MFAS_EINVAL, "null argument or K <= 0");
     if (hp->R < 1 || hp->R > 512 || hp->C < 1 || hp->C > 256) return fail(MFAS_EINVAL, "R must be in [1,512], C in [1,256]");
-    if (hp->B < 2 || hp->B > 64) return fail(MFAS_EINVAL, "batchsize must be in [2,64]");
-    {
-        const int bp = ((hp->B + 15) / 16 == 3 ? 4 : (hp->B + 15) / 16) * 16, lpr = std::min(16, 512 / bp);
-        if (((hp->C + 15) & ~15) > 8 * lpr) return fail(MFAS_EINVAL, "num_outputs too large for this batch size (C_padded <= 8 * min(16, 512/B_padded))");
-    }
+    if (hp->B < 2 || hp->B > 128) return fail(MFAS_EINVAL, "batchsize must be in [2,128]");
     if (!(hp->drpt > 1e-10) && !hp->bn && !hp->allow_plain_cell)   // ntu_searchable.py:274-284: `op` never assigned
         return fail(MFAS_EINVAL, "illegal cell variant: drpt < 1e-10 without batchnorm (reference: UnboundLocalError)");
     if (hp->drpt >= 1.0) return fail(MFAS_EINVAL, "drpt must be < 1");
@@ -134,6 +130,14 @@ static int validate_inputs(const mfas_hyper* hp, const int32_t* confs, const int
         }
     }
     return MFAS_OK;
+}
+
+// What the batch-resident kernels (chain_body / chain_lean / sweep_body: the whole padded batch in LDS, MB <= 4 as a template
+// parameter, softmax with <= 8 classes per lane) cannot take whatever the LDS says: such a geometry trains on the wide path
+// (wide.hip.h), like one whose step does not fit the LDS (plan_layout).
+static bool batch_resident_refuses(const mfas_hyper* hp) {
+    const int bp = ((hp->B + 15) / 16 == 3 ? 4 : (hp->B + 15) / 16) * 16, lpr = std::min(16, 512 / bp);
+    return hp->B > 64 || ((hp->C + 15) & ~15) > 8 * lpr;
 }
 
 static Geo make_geo(const mfas_hyper* hp) {      // (the step-buffer offsets sb_* depend on the widest candidate: plan_layout fills them in)
@@ -174,6 +178,11 @@ static size_t sweep_unit_lds(const Geo& g, const SegDesc& d) {
     if (nrb < STEP_NW && d.kind <= KIND_V) fl += (size_t)STEP_NW * nrb * g.MB * 256;
     return fl * 4;
 }
+// the wide path (wide.hip.h): a sweep unit's batch slice of x_t, x_{t+1} and dy; the chain's rows in flight, logits and statistics
+static size_t wide_unit_lds(const SegDesc& d) {
+    return wide_sweep_lds_floats(std::min(16 * WIDE_KB, d.cc), std::min(16 * WIDE_RBG, d.rows_p)) * 4;
+}
+static size_t wide_chain_lds(const Geo& g) { return wide_chain_lds_floats(g.Rp, g.Cp, g.Bp) * 4; }
 // a candidate's vector block, three planes
 static size_t vec_lds(const Geo& g) { return (size_t)3 * (MFAS_MAX_CELLS * g.vec_cell_stride + g.Cp) * 4; }
 // chain_lean: out_i / dy_i of all cells, logits, misc, reduced sums, vector block, saved activations
@@ -312,6 +321,9 @@ struct LayoutPlan {
     int res_nu = 1;                  // resident units per workgroup (2: a workgroup serves units of two candidates)
     int nres_wg = 0;                 // resident workgroups = ceil(nres / res_nu)
     int res_buf_words = 0;           // LDS words of one staged batch of a resident unit
+    bool wide = false;               // the wide path (wide.hip.h: k_chain_wide + k_sweep_wide, launch per phase, batch walked in tiles): exactly
+                                     // the geometries the batch-resident kernels refuse; no resident / same-group / chain_split / A-B schedule
+    std::vector<int> wide_start;     // [K+1] first wide unit of every candidate in groups[0].descs (candidate-major)
     bool lean_chain = false;         // chain_lean (R <= 16, C <= 64, B <= 32) in standalone and fused launches
     bool same_group = false;         // one launch per step: chain blocks + sweep blocks of the same candidates, per-cell dy flags (k_step_same)
     int chain_split = 0;             // CUs per candidate chain in the same-group launch (0 / 1: chain_body on one CU; 4: chain_split<4>)
@@ -331,17 +343,24 @@ struct LayoutPlan {
     std::vector<int32_t> role;       // [K + nres_wg] role of every workgroup of the resident launch (XCD-aware placement); empty: block b runs role b
 };
 
-static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int K, int chunk_cols,
-                       int n_cus, bool allow_persist, const Tuning& tu, LayoutPlan& pl) {
+static int plan_layout_as(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int K, int chunk_cols,
+                          int n_cus, bool allow_persist, const Tuning& tu, const bool wide, LayoutPlan& pl) {
     pl = LayoutPlan();
+    pl.wide = wide;
     Geo& g = pl.g;
     g = make_geo(hp);
     const int vec_size = (g.vec_head + g.Cp + 63) & ~63;
 
     // ---- column chunk per workgroup and the schedule
-    ChunkPlan lp = plan_chunk(hp, g, confs, n_cells, K, chunk_cols, n_cus, allow_persist, tu);
-    if (lp.res_ok && !lp.resident)    // units were chosen for the resident schedule, which does not stand: the launch-per-phase chunking
-        lp = plan_chunk(hp, g, confs, n_cells, K, chunk_cols, n_cus, false, tu);
+    ChunkPlan lp;
+    if (wide) {      // feature chunks of <= 8 k-blocks: one wide unit keeps a chunk's dW tiles of its row block in registers
+        lp.target = chunk_cols > 0 ? std::min(16 * WIDE_KB, chunk_cols) : 16 * WIDE_KB;
+        lp.target = std::max(16, (lp.target / 16) * 16);
+    } else {
+        lp = plan_chunk(hp, g, confs, n_cells, K, chunk_cols, n_cus, allow_persist, tu);
+        if (lp.res_ok && !lp.resident)    // units were chosen for the resident schedule, which does not stand: the launch-per-phase chunking
+            lp = plan_chunk(hp, g, confs, n_cells, K, chunk_cols, n_cus, false, tu);
+    }
     const int target = pl.chunk = lp.target;
     pl.cands.resize(K);
     pl.desc_start.assign(K + 1, 0);
@@ -461,7 +480,10 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
     pl.bytes_per_launch = alg_bytes + 4.0 * alg_feat;
 
     // ---- LDS budgets
-    {
+    if (wide) {
+        for (const SegDesc& d : pl.descs) pl.lds_step = std::max(pl.lds_step, wide_unit_lds(d));
+        pl.lds_chain = wide_chain_lds(g);
+    } else {
         // resident feature units (persistent schedule) do not go through sweep_body: their LDS need is separate
         pl.persist = lp.resident;
         pl.res_chain = lp.res_ok;
@@ -496,7 +518,7 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
         pl.lds_eval = ((size_t)ME * std::max(EVAL_CE + 8, g.Cp + 4) + (size_t)ME * (g.Rp + 8)) * 4;   // strides: eval.hip.h
         if (pl.lds_eval <= 80 * 1024) break;
     }
-    pl.fits_lds = !(pl.mbe < 1 || pl.nrbw > 8 || pl.lds_step > 150 * 1024);     // (create refuses what does not fit; the plan query still answers)
+    pl.fits_lds = !(pl.mbe < 1 || pl.nrbw > 8 || pl.lds_step > 150 * 1024 || (wide && pl.lds_chain > 150 * 1024));     // (create refuses what does not fit; the plan query still answers)
 
     {   // candidate groups: two halves balanced by work (descriptor columns), contiguous ranges
         // Two groups (the chain of one runs under the sweep of the other).  Measured on MI355X (cand/s, unfused vs fused):
@@ -507,7 +529,7 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
         // (R=128 cand/s unfused+reduce vs fused+reduce: 12 candidates 18.1 vs 20.2, 16: 21.0 vs 23.6, 24: 22.9 (old default) vs 26.6)
         int ngroups = pl.lean_chain ? ((K >= 40 && K < 224) ? 2 : 1) : (K >= 8 ? 2 : 1);
         if (tu.groups > 0) ngroups = (tu.groups >= 2 && K >= 2) ? 2 : 1;
-        if (pl.persist) ngroups = 1;
+        if (pl.persist || wide) ngroups = 1;
         // same-group fused launch (k_step_same): general chain, one group, R >= 128 (no tap-major units), launch-per-phase
         {
             const int sgenv = tu.same_group;     // 0: never, 2: whatever the size (A/B runs)
@@ -517,7 +539,7 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
             double state_bytes = 0;
             for (const SegDesc& d : pl.descs) state_bytes += 24.0 * d.cc * d.rows_p;
             const bool two_forced = tu.groups >= 2;      // (tests: the two-group fused schedule)
-            pl.same_group = !pl.persist && !pl.lean_chain && g.MB <= 2 && (state_bytes <= 260e6 || sgenv == 2) && sgenv != 0 && !two_forced;
+            pl.same_group = !wide && !pl.persist && !pl.lean_chain && g.MB <= 2 && (state_bytes <= 260e6 || sgenv == 2) && sgenv != 0 && !two_forced;
         }
         if (pl.same_group) ngroups = 1;
         // the chain of one candidate over 4 CUs (chain.hip.h, chain_split): eight row blocks, one batch tile, <= 4 class blocks, no alphas
@@ -550,7 +572,7 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
             std::vector<SegDesc>& sorted = gr.descs;
             std::vector<TapDesc>& taps = gr.taps;
             // (tap-major workgroups stage a batch's rows ONCE for several candidates: not with per-candidate sample orders)
-            const bool tap_major = (g.nrb == 1 || g.nrb == 2 || g.nrb == 4) && !tu.no_tap_major && !pl.persist && !pl.same_group &&
+            const bool tap_major = !wide && (g.nrb == 1 || g.nrb == 2 || g.nrb == 4) && !tu.no_tap_major && !pl.persist && !pl.same_group &&
                                    !hp->order_per_candidate;
             if (tap_major) {
                 const int per_wg = STEP_NW / g.nrb;
@@ -583,6 +605,30 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
             } else {
                 sorted = all;
             }
+            if (wide) {
+                // wide units: <= 8 row blocks (one per wave) x <= 8 k-blocks of a layout chunk, candidate-major (train-mode single batches
+                // launch one candidate's range).  The plane layout is the batch-resident one — OUT / HEAD stay ONE chunk of Rp columns, which the
+                // chain, the dev pass and the packers index — so their units name a k-block range inside it (SegDesc::sub_kb0 / sub_nkb).
+                std::vector<SegDesc> fine;
+                pl.wide_start.assign(K + 1, 0);
+                for (int k = gr.c0; k < gr.c0 + gr.nc; ++k) {
+                    pl.wide_start[k] = (int)fine.size();
+                    for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) {
+                        const SegDesc& d = pl.descs[j];
+                        const int nrb_d = d.rows_p / 16, nkb_d = d.cc / 16;
+                        for (int r0 = 0; r0 < nrb_d; r0 += WIDE_RBG)
+                            for (int q0 = 0; q0 < nkb_d; q0 += WIDE_KB) {
+                                SegDesc u = d;
+                                u.rb0 = r0; u.rows_p = 16 * std::min(WIDE_RBG, nrb_d - r0); u.seg_nrb = nrb_d;
+                                u.w_off = d.w_off + (int64_t)r0 * nkb_d * 256;
+                                u.sub_kb0 = q0; u.sub_nkb = std::min(WIDE_KB, nkb_d - q0);
+                                fine.push_back(u);
+                            }
+                    }
+                }
+                pl.wide_start[K] = (int)fine.size();
+                sorted.swap(fine);
+            } else
             std::stable_sort(sorted.begin(), sorted.end(), [](const SegDesc& x, const SegDesc& y) {
                 return (int64_t)x.cc * x.rows_p > (int64_t)y.cc * y.rows_p; });
             if (pl.same_group) {
@@ -616,7 +662,7 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
     // (not with chain_split: the reducing unit's drain + arrival + summing pass behind the LAST dy of the step ends the launch 3.5 us later,
     //  while the chain's four parts sum their own row blocks of the slabs at entry, every load in flight at once; measured, K = 1: 41.3 with
     //  the reduction in the sweep, 38.4 without, 43.0 with a hybrid — cells >= 1 in the sweep, cell 0 in the chain — profiles/r06_chain_split_r128.log)
-    pl.red_in_sweep = K < 28 && !pl.lean_chain && !pl.persist && !tu.no_red_in_sweep && !(pl.chain_split && pl.same_group);
+    pl.red_in_sweep = !wide && K < 28 && !pl.lean_chain && !pl.persist && !tu.no_red_in_sweep && !(pl.chain_split && pl.same_group);
     for (const auto& gr : pl.groups) if (!gr.taps.empty()) pl.red_in_sweep = false;     // (tap-major workgroups serve several candidates)
     if (pl.chain_split) {
         pl.lds_split = std::max(pl.lds_step, chain_split_lds_floats<4>(g.Rp, g.Cp) * 4);
@@ -684,4 +730,16 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
     pl.nontemporal = (double)pl.plane_stride * 12.0 > 200.0 * 1024 * 1024;
     if (tu.nt >= 0) pl.nontemporal = tu.nt != 0;
     return MFAS_OK;
+}
+
+// The plan of a population: the batch-resident schedules wherever they hold the geometry — decided exactly as before the wide path
+// existed, so every such population keeps its layout, kernels and bits — and the wide path exactly where they do not: B > 64, more
+// classes than the batch-resident softmax takes, or a step that does not fit the LDS.
+static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int K, int chunk_cols,
+                       int n_cus, bool allow_persist, const Tuning& tu, LayoutPlan& pl) {
+    if (!batch_resident_refuses(hp)) {
+        if (int rc = plan_layout_as(hp, confs, n_cells, drop_seeds, K, chunk_cols, n_cus, allow_persist, tu, false, pl)) return rc;
+        if (pl.fits_lds) return MFAS_OK;
+    }
+    return plan_layout_as(hp, confs, n_cells, drop_seeds, K, chunk_cols, n_cus, allow_persist, tu, true, pl);
 }

@@ -446,7 +446,8 @@ class Population:
         d = dict(zip(keys, (int(x) for x in info)))
         # info[5] bits 8..15: CUs one candidate's general chain runs on in the same-group launch (round 6: chain_split; 1 otherwise)
         d["chain_cus"] = max(1, (d["lean_chain"] >> 8) & 0xFF)
-        d["lean_chain"] &= 0xFF
+        d["wide"] = (d["lean_chain"] >> 1) & 1      # bit 1: the wide path (k_chain_wide + k_sweep_wide, launch per phase)
+        d["lean_chain"] &= 1
         return d
 
     def sweep_profile(self):
@@ -476,7 +477,7 @@ def plan_population(hp: Hyper, confs: Sequence[np.ndarray], device, chunk_cols: 
     hc = hp.to_c()
     _lib.check(lib.mfas_population_plan(C.byref(hc), cf.ctypes.data, nc.ctypes.data, len(confs), int(idx), int(chunk_cols), info.ctypes.data))
     return {"persistent": bool(info[0]), "resident_units": int(info[1]), "resident_workgroups": int(info[2]),
-            "units_per_workgroup": int(info[3]), "chunk_cols": int(info[4]), "lean_chain": bool(info[5]), "compute_units": int(info[6]),
+            "units_per_workgroup": int(info[3]), "chunk_cols": int(info[4]), "lean_chain": bool(info[5] & 1), "wide": bool(info[5] & 2), "compute_units": int(info[6]),
             "candidates": int(info[7])}
 
 

@@ -219,7 +219,7 @@ class Searchable_Skeleton_Image_Net(nn.Module):
     def forward(self, tensor_tuple):
         """tensor_tuple = (rgb, ske): dict-likes holding the pooled taps v0..v3 [+ 'vlogit'] and s0..s3
         [+ 'slogit'] on a HIP device.  Eval mode: running-statistics BatchNorm, no Dropout (mfas_population_forward).  Train mode:
-        one batch of <= 64 samples with batch statistics and Dropout, differentiable with respect to the central parameters
+        one batch of <= 128 samples with batch statistics and Dropout, differentiable with respect to the central parameters
         (_TrainModeForward).  The taps are outputs of frozen backbones here (feature tables): no gradient flows into them, and
         taps that require grad are refused instead of being silently cut off.  The fast path for training stays
         train_sampled_models / train_ntu_track_acc."""
@@ -243,8 +243,8 @@ class Searchable_Skeleton_Image_Net(nn.Module):
             # num_batches_tracked move — and Dropout (the engine's counter-based stream, seeded from torch's RNG).  The logits carry
             # an autograd edge to the central parameters (_TrainModeForward: loss.backward() runs the engine's fused backward);
             # the fast path for training stays train_ntu_track_acc / train_sampled_models.
-            if not 1 <= n <= 64:
-                raise NotImplementedError("train-mode forward handles one batch of 1..64 samples (the engine's batch range)")
+            if not 1 <= n <= 128:
+                raise NotImplementedError("train-mode forward handles one batch of 1..128 samples (the engine's batch range)")
             if n == 1 and self.args.batchnorm:
                 raise ValueError("Expected more than 1 value per channel when training")     # torch BatchNorm1d's message
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())

@@ -243,6 +243,13 @@ def representative_conf(hp) -> np.ndarray:
     return np.array([[s_idx[i % len(s_idx)], v_idx[i % len(v_idx)], i % 2] for i in range(4)], np.int64)
 
 
+def wide_geometry(hp, conf, device, chunk_cols: int = 0) -> bool:
+    """Does a population of this geometry take the wide path (batch above 64, more classes than the batch-resident softmax takes,
+    a step beyond the LDS: launch per phase only, no resident schedule)?  The engine's layout query, nothing allocated."""
+    from .engine import plan_population
+    return bool(plan_population(hp, [conf], device if device is not None else "cuda:0", chunk_cols).get("wide"))
+
+
 def split_rounds(hp, confs, device, chunk_cols: int = 0, min_candidates: int = 16):
     """How a rank's share trains: ONE population, or several resident rounds one after the other when the share does not fit the
     resident schedule as a whole (R <= 16: parameters in registers, <= ~28 conf-4-sized candidates) — every round but the last
@@ -259,6 +266,8 @@ def split_rounds(hp, confs, device, chunk_cols: int = 0, min_candidates: int = 1
         return bool(plan_population(hp, [confs[i] for i in pos], device, chunk_cols)["persistent"])
 
     everything = list(range(n))
+    if wide_geometry(hp, confs[0], device, chunk_cols):     # the wide path has no resident form at any size: nothing to bisect
+        return [(everything, False)]
     if hp.R > 16 or os.environ.get("MFAS_NO_ROUNDS"):
         return [(everything, hp.R <= 16 and resident(everything))]
     if resident(everything):
@@ -395,6 +404,7 @@ def step_model(hp, device=None) -> StepModel:
     rank, world = dist_info()
     use_device = device is not None and torch.device(device).type == "cuda" and torch.cuda.is_available() and not os.environ.get("MFAS_NO_CALIBRATE")
     res_pts, str_pts, calibrated = [], [], False
+    has_resident = hp.R <= 16 and not wide_geometry(hp, rep, device)
     NPT = 4
     buf = np.zeros(1 + 4 * NPT, np.float64)
     if use_device and rank == 0:
@@ -402,7 +412,7 @@ def step_model(hp, device=None) -> StepModel:
             from .engine import plan_population
             hq = copy.copy(hp)
             cap = 0
-            if hp.R <= 16:
+            if has_resident:
                 lo, hi = 1, 96
                 while lo <= hi:
                     mid = (lo + hi) // 2
@@ -436,7 +446,7 @@ def step_model(hp, device=None) -> StepModel:
         res_pts = [(buf[1 + 2 * j], buf[2 + 2 * j]) for j in range(NPT) if buf[1 + 2 * j] > 0]
         str_pts = [(buf[1 + 2 * NPT + 2 * j], buf[2 + 2 * NPT + 2 * j]) for j in range(NPT) if buf[1 + 2 * NPT + 2 * j] > 0]
     else:                                # the constants of the box this repository was tuned on
-        if hp.R <= 16:
+        if has_resident:
             res_pts = [(1.0, RESIDENT_STEP_US[0][1])] + [(float(c), us) for c, us in RESIDENT_STEP_US]
             str_pts = [(float(k), max(38.0, 12.0 + 24.0 * k * rep_cost / STREAM_BYTES_PER_US)) for k in (29, 64, 128)]
         else:

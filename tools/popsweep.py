@@ -1,6 +1,6 @@
 """Small-population sweep: candidates/s of one train_sampled_models-sized job (E epochs over N_train / N_dev) for K candidates on
 one GPU, launch-per-phase schedule (MFAS_PERSIST=0) vs the default policy (persistent resident step loop where it fits), each with its own default unit
-decomposition.  usage: popsweep.py R B bn E K1,K2,... [mixed] [N_train N_dev]"""
+decomposition.  usage: popsweep.py R B bn E K1,K2,... [mixed] [N_train N_dev]   |   popsweep.py wide  (batch-64 rows, see wide_rows)"""
 import os
 import sys
 import time
@@ -11,6 +11,51 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mfas_amd as M
 from oracle import np_oracle as O
+
+
+def wide_rows():
+    """usage: popsweep.py wide — us per train step of conf-4 populations at batch 64 (R = 256: the wide path; R = 128: the widest
+    batch-resident shape at that batch) next to the same widths at batch 32, K = 1, 16, 64, bf16 taps, BatchNorm, shared order.
+    A step's time is the difference of a 240- and a 40-step call (best of three each, after one warm-up call) over 200 steps;
+    bytes per step from the byte model (24 P + B * sum(F) * 2 + 8 B per candidate)."""
+    dev = torch.device("cuda:0")
+    conf4 = np.array([[3, 1, 1], [1, 3, 0], [1, 1, 1], [3, 3, 0]])
+    T1, T2 = 40, 240
+    print("# R B K: schedule, us/step, rows/s, MB/step (byte model), fraction of 8 TB/s")
+    for R, B in ((256, 64), (256, 32), (128, 64), (128, 32)):
+        hp = M.Hyper(R=R, B=B, bn=True, drpt=0.5, tap_bits=16)
+        N = T2 * B
+        tr = M.FeatureTable.synthetic(N, 1, dev, torch.bfloat16, snr=0.12)
+        etas = np.full(T2, 1e-3)
+        order = M.ntu_searchable.make_order(N, 1, True, 5, dev)
+        feat = sum(hp.s_sizes[c[0]] + hp.v_sizes[c[1]] for c in conf4)
+        P = sum(R * (hp.s_sizes[c[0]] + hp.v_sizes[c[1]] + (R if i else 0)) for i, c in enumerate(conf4)) + hp.C * R
+        for K in (1, 16, 64):
+            pop = M.Population(hp, [conf4] * K, dev, drop_seeds=list(range(100, 100 + K)))
+            try:
+                pop.init(list(range(1, K + 1)))
+                sched = pop.schedule()
+                best = {}
+                for T in (T1, T1, T2, T1, T2, T1, T2):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    pop.train(tr, None, 1, etas, order=order, max_steps=T)
+                    dt = time.perf_counter() - t0
+                    if T != T1 or "warm" in best:
+                        best[T] = min(best.get(T, 1e30), dt)
+                    best["warm"] = 1
+            finally:
+                pop.close()
+            us = (best[T2] - best[T1]) / (T2 - T1) * 1e6
+            mb = K * (24.0 * P + B * feat * 2 + 8 * B) / 1e6
+            name = "wide" if sched.get("wide") else ("same-group" if sched["groups"] == -1 else f"{sched['groups']} group(s)")
+            print(f"R={R:3d} B={B:2d} K={K:2d}  {name:10s} {us:8.1f} us/step  {K * B / us * 1e6:12.0f} rows/s  {mb:8.1f} MB/step  "
+                  f"{mb / us / 8e6 * 1e6:.3f} of 8 TB/s", flush=True)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "wide":
+    wide_rows()
+    sys.exit(0)
 
 R, B, bn, E = (int(x) for x in sys.argv[1:5])
 Ks = [int(x) for x in sys.argv[5].split(",")]
