@@ -107,8 +107,9 @@ void mfas_population_destroy(mfas_population* pop);
 int64_t mfas_population_param_count(const mfas_population* pop, int32_t k);
 
 /* Load / read back candidate k's parameters (device float buffers in the order above).
- * plane 0 = parameters, 1 = Adam exp_avg, 2 = Adam exp_avg_sq.  set() also zeroes the Adam state
- * and the step counter (a fresh torch.optim.Adam, ntu_searchable.py:65). */
+ * plane 0 = parameters, 1 = Adam exp_avg, 2 = Adam exp_avg_sq, 3 (get only; mfas_population_set_state writes it) = the kept
+ * best-epoch parameters of a snapshot_best schedule driven through mfas_population_train_from (MFAS_EINVAL when candidate k keeps
+ * none).  set() also zeroes the Adam state and the step counter (a fresh torch.optim.Adam, ntu_searchable.py:65). */
 int mfas_population_set_params(mfas_population* pop, int32_t k, const float* flat);
 int mfas_population_get_params(mfas_population* pop, int32_t k, int32_t plane, float* flat);
 
@@ -135,11 +136,55 @@ int mfas_population_init_torch_streams(mfas_population* pop, const uint64_t* see
  * epochs do not run; debug/known-answer tests; dev evaluation is skipped).  stats: HOST [K][epochs].  status: HOST [K], 1 =
  * non-finite loss seen.
  * snapshot_best != 0 keeps the best-dev-epoch parameters and restores them at the end (:82-86).
- * Every call starts from zeroed Adam moments and step count (a freshly constructed optimizer). */
+ * Every call starts from zeroed Adam moments and step count (a freshly constructed optimizer); a schedule that has to stop and go
+ * on is driven through mfas_population_train_from below. */
 int mfas_population_train(mfas_population* pop, const mfas_table* train, const mfas_table* dev,
                           const int32_t* order, const float* step_scalars, int32_t epochs,
                           int64_t max_steps, int32_t snapshot_best, mfas_epoch_stats* stats,
                           int32_t* status);
+
+/* ---- Resume: stop after an epoch and go on later — in the same handle, in another population, from a file -------------------
+ * What train_ntu_track_acc keeps on its stack for the length of one call (train_searchable/ntu.py:17-18: best_model_sd = a copy
+ * of the initial state_dict, best_acc = 0; :82-86: strict '>' replaces both, the best state is loaded at the end) and what
+ * torch.optim.Adam keeps in its state (exp_avg, exp_avg_sq, step) is kept in the population between calls instead: planes 1 / 2,
+ * the kept best-epoch plane 3, and a per-candidate PROGRESS RECORD {epochs of the schedule that are complete, the schedule's
+ * batches per epoch nb, best dev metric so far, whether the schedule keeps the best epoch}.  The step counter needs no storage:
+ * step t of epoch e is e * nb + t for the step scalars, the dropout stream, the sample order and the statistics slot alike, and
+ * nothing in the step buffers crosses an epoch boundary — a schedule run in segments is BIT-IDENTICAL to the one-call run. */
+
+/* Epochs [first_epoch, last_epoch) of a schedule of `epochs` epochs.  order, step_scalars and stats are indexed exactly as in
+ * mfas_population_train and sized for the WHOLE schedule; stats columns outside the segment come back zero.
+ * first_epoch == 0 does what mfas_population_train does at entry: zeroes the Adam moments, sets every best metric to the best
+ * threshold and the kept best parameters to a copy of the initial ones (:17-18), clears status.  first_epoch > 0 zeroes nothing
+ * (status is sticky across segments) and requires every candidate's progress record to say that exactly first_epoch epochs of a
+ * schedule with the same nb and the same snapshot_best are complete — otherwise MFAS_EINVAL (the message names both numbers) and
+ * nothing is changed.  snapshot_best restores the best parameters (:86) only when last_epoch == epochs: an unfinished schedule is
+ * left with its LIVE parameters in plane 0 and the kept best in plane 3.  There is no max_steps here.
+ * mfas_population_train itself is unchanged; it RESETS the record (0 epochs complete). */
+int mfas_population_train_from(mfas_population* pop, const mfas_table* train, const mfas_table* dev, const int32_t* order,
+                               const float* step_scalars, int32_t epochs, int32_t first_epoch, int32_t last_epoch,
+                               int32_t snapshot_best, mfas_epoch_stats* stats, int32_t* status);
+
+/* Write ONE plane of candidate k from a device float buffer in the state_dict order above and touch nothing else: plane 1 / 2 =
+ * Adam exp_avg / exp_avg_sq, 3 = the kept best-epoch parameters (the candidate's record then says its schedule keeps the best
+ * epoch).  Plane 0 stays with mfas_population_set_params (which zeroes the moments: write them AFTER it).  Asynchronous on the
+ * population's stream like set_params: keep `flat` alive until the stream has been synchronised. */
+int mfas_population_set_state(mfas_population* pop, int32_t k, int32_t plane, const float* flat);
+
+/* Candidate k's progress record and status word (HOST pointers).  get: every pointer may be NULL.  set: a NULL pointer leaves
+ * that entry as it is; epochs_done = 0 makes the candidate a fresh one (its record no longer keeps a best epoch). */
+int mfas_population_get_progress(mfas_population* pop, int32_t k, int64_t* epochs_done, int64_t* nb, double* best_metric,
+                                 int32_t* status);
+int mfas_population_set_progress(mfas_population* pop, int32_t k, const int64_t* epochs_done, const int64_t* nb,
+                                 const double* best_metric, const int32_t* status);
+
+/* Candidate ks of `src` into slot kd of `dst` with everything it trains on: W, m, v, the kept best, the BatchNorm running
+ * statistics, the progress record and the status word.  Device to device on dst's stream through the flat state_dict order — the
+ * two populations' layouts may differ (chunk size, resident or not, wide or not); no host copy, and the only synchronisation is
+ * that of src's stream when it is not dst's.  MFAS_EINVAL when the two candidates' configurations, or the hyper-parameters that
+ * define a candidate's parameters (R, C, bn, alphas, tap widths), differ.  The dropout seed belongs to the SLOT: create dst with
+ * the seed the moved candidate trained under. */
+int mfas_population_move(mfas_population* dst, int32_t kd, mfas_population* src, int32_t ks);
 
 /* Replaces Searchable_Skeleton_Image_Net.forward in eval mode (ntu_searchable.py:206-247) for
  * candidate k on rows [row0, row0+nrows) of a table: writes logits (nrows, C) (device, row-major);

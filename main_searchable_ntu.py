@@ -54,6 +54,9 @@ def parse_args(argv=None):
     p.add_argument("--engine_order", default="per_candidate", choices=["shared", "per_candidate"],
                    help="per_candidate (default): every candidate draws its own permutations, as the reference's per-candidate "
                         "DataLoader(shuffle=True) does (models/searchable.py:248-250); shared: one shuffled order per epoch for the whole call (lockstep)")
+    p.add_argument("--engine_halving", type=int, nargs="+", metavar=("ETA", "R1"), default=None,
+                   help="successive halving inside every train_sampled_models call: after epochs R1 [R2 ...] only the best 1/ETA of the "
+                        "candidates (by dev accuracy so far) train on; one GPU, no --weightsharing")
     p.add_argument("--engine_all_ranks", action="store_true", default=False,
                    help="under torchrun: shard every call over ALL ranks (default: only as many ranks as the calibrated step-time model "
                         "says shorten the call, mfas_amd/population.py)")
@@ -67,7 +70,12 @@ def parse_args(argv=None):
     p.add_argument("--timing", action="store_true", help="print how the wall time splits into candidate training (GPU) and the controller / surrogate (CPU)")
     p.add_argument("--controller_threads", type=int, default=4,
                    help="torch CPU threads for the 81k-parameter surrogate (more threads only add overhead)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.engine_halving is not None:      # ETA R1 [R2 ...] -> (eta, rungs), what train_sampled_models reads
+        if len(args.engine_halving) < 2:
+            p.error("--engine_halving ETA R1 [R2 ...]: at least one rung")
+        args.engine_halving = (args.engine_halving[0], tuple(args.engine_halving[1:]))
+    return args
 
 
 def main(argv=None):

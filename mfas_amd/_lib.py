@@ -74,6 +74,12 @@ def lib():
     L.mfas_range_push.argtypes = [C.c_char_p]
     L.mfas_population_init_torch_streams.argtypes = [P, P, P, C.c_double, C.c_double]
     L.mfas_tuning_describe.argtypes = [C.c_char_p, C.c_int32]
+    L.mfas_population_train_from.argtypes = [P, C.POINTER(mfas_table), C.POINTER(mfas_table), P, P, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, P, P]
+    L.mfas_population_set_state.argtypes = [P, C.c_int32, C.c_int32, P]
+    L.mfas_population_get_progress.argtypes = [P, C.c_int32, P, P, P, P]
+    L.mfas_population_set_progress.argtypes = [P, C.c_int32, P, P, P, P]
+    L.mfas_population_move.argtypes = [P, C.c_int32, P, C.c_int32]
     _lib = L
     return L
 
@@ -83,7 +89,9 @@ EXPORTS = ["mfas_last_error", "mfas_version", "mfas_population_create", "mfas_po
            "mfas_population_init", "mfas_population_train", "mfas_population_forward",
            "mfas_population_sweep_profile", "mfas_population_set_profiling", "mfas_population_set_pos_weight", "mfas_global_pool", "mfas_stream_probe", "mfas_source_digest",
            "mfas_population_set_best_threshold", "mfas_population_forward_train", "mfas_population_schedule",
-           "mfas_population_plan", "mfas_population_backward", "mfas_range_push", "mfas_range_pop", "mfas_population_init_torch_streams", "mfas_tuning_describe"]
+           "mfas_population_plan", "mfas_population_backward", "mfas_range_push", "mfas_range_pop", "mfas_population_init_torch_streams", "mfas_tuning_describe",
+           "mfas_population_train_from", "mfas_population_set_state", "mfas_population_get_progress", "mfas_population_set_progress",
+           "mfas_population_move"]
 
 
 def tuning() -> dict:

@@ -143,6 +143,17 @@ struct mfas_population {
     int64_t prof_launches = 0;
     double prof_ms = 0.0, bytes_per_launch = 0.0, prof_bytes = 0.0;
     double best_threshold = 0.0;    // snapshot_best: a dev metric must exceed this to count (init_f1, mmimdb.py:18; 0 for NTU)
+    // Progress record (mfas_population_train_from): what train_ntu_track_acc keeps on its stack for one call (best_acc,
+    // train_searchable/ntu.py:18,82-83) and where in its schedule every candidate stands, kept between calls.  Per candidate: a moved
+    // candidate (mfas_population_move) brings its own.
+    struct Progress {
+        std::vector<int64_t> done, nb;      // epochs of the schedule that are complete; that schedule's batches per epoch
+        std::vector<double> best_metric;    // best dev metric so far (starts at best_threshold)
+        std::vector<int32_t> keeps_best;    // the schedule runs with snapshot_best: plane `best` holds this candidate's best epoch
+        void reset(int K, double threshold) { done.assign(K, 0); nb.assign(K, 0); best_metric.assign(K, threshold); keeps_best.assign(K, 0); }
+    } prog;
+    float* d_move = nullptr;        // mfas_population_move: one candidate in flat state_dict order (grow-only scratch of the destination)
+    int64_t move_cap = 0;
     uint32_t* d_red_cnt = nullptr;  // reduce-in-sweep arrival counters [K][4] (small populations, general chain)
     char* d_gather = nullptr;       // gathered rows [K][2 parities][taps][Bp][width] (two-group schedule, per-candidate orders; sweep.hip.h)
     size_t gather_cap = 0;
@@ -310,6 +321,7 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
     p->stream = reinterpret_cast<hipStream_t>(hip_stream);
     p->chunk_cols_req = chunk_cols;
     p->n_cus = device_cus(device);
+    p->prog.reset(K, 0.0);
     if (int prc = plan_layout(hp, confs, n_cells, drop_seeds, K, chunk_cols, p->n_cus, allow_persist, p->tune, p->plan)) { delete p; return prc; }
     const LayoutPlan& pl = p->plan;
     if (!pl.fits_lds) { delete p; return fail(MFAS_EINVAL, "geometry does not fit the 160 KiB LDS (R / batchsize too large)"); }
@@ -400,6 +412,7 @@ extern "C" void mfas_population_destroy(mfas_population* p) {
     hipFree(p->d_gather);
     hipFree(p->d_cellflag);
     hipFree(p->d_xch);
+    hipFree(p->d_move);
     hipFree(p->d_sync); hipFree(p->d_need); hipFree(p->d_role); hipFree(p->d_scal); hipFree(p->d_trace); hipFree(p->d_pdescs);
     delete p;
 }
@@ -430,10 +443,13 @@ extern "C" int mfas_population_set_params(mfas_population* p, int32_t k, const f
 }
 
 extern "C" int mfas_population_get_params(mfas_population* p, int32_t k, int32_t plane, float* flat) {
-    if (!p || !flat || k < 0 || k >= p->K || plane < 0 || plane > 2) return fail(MFAS_EINVAL, "bad argument");
+    if (!p || !flat || k < 0 || k >= p->K || plane < 0 || plane > 3) return fail(MFAS_EINVAL, "bad argument");
+    if (plane == 3 && !(p->best && p->prog.keeps_best[k]))
+        return fail(MFAS_EINVAL, "plane 3: candidate " + std::to_string(k) + " keeps no best-epoch parameters (no snapshot_best schedule in progress)");
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(hipMemsetAsync(flat, 0, sizeof(float) * p->plan.nparams[k], p->stream));
-    PackArgs a = pack_args(p, PK_GET, plane, flat);
+    PackArgs a = pack_args(p, PK_GET, plane == 3 ? 0 : plane, flat);
+    if (plane == 3) a.plane = p->best;      // (a full image of plane 0, BatchNorm running statistics included)
     a.desc = p->d_descs + p->plan.desc_start[k];
     const int n = p->plan.desc_start[k + 1] - p->plan.desc_start[k];
     hipLaunchKernelGGL(k_pack, dim3(n), dim3(256), 0, p->stream, a);
@@ -664,6 +680,7 @@ static int persist_fallback(mfas_population* p) {
     std::swap(q->d_scal, p->d_scal);
     std::swap(q->scal_cap, p->scal_cap);
     q->best_threshold = p->best_threshold;
+    q->prog = p->prog;
     q->profiling = p->profiling;
     q->prof_every = p->prof_every;
     q->ev.swap(p->ev);
@@ -725,6 +742,17 @@ static hipError_t init_args(TrainCall& c) {     // (again after persist_fallback
     st.ca.xch = p->d_xch; st.ca.nsplit = pl.chain_split; st.ca.xpar = 0;
     c.split_launches[0] = c.split_launches[1] = 0;
     return e_;
+}
+
+// chain_split in the same-group launch counts ARRIVALS on the per-cell flags: every part adds 1 per step and a sweep unit waits for
+// parts * (gstep + 1).  init_args zeroes the flags, which is right for a call that starts at step 0; one that starts at epoch `ep`
+// (a later segment of a schedule, or the launch-per-phase layout taking over mid-call) starts them where steps 0 .. ep * nb - 1
+// would have left them.  (The one-part chain stores its target and needs nothing.)
+static hipError_t seed_cellflags(TrainCall& c, int64_t ep) {
+    mfas_population* p = c.p;
+    if (ep <= 0 || !p->plan.same_group || !p->plan.chain_split) return hipSuccess;
+    return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->d_cellflag), (int)((uint32_t)p->plan.chain_split * (uint32_t)(ep * c.nb)),
+                             (size_t)p->K * CELLFLAG_STRIDE, p->stream);
 }
 
 static hipError_t setup_gather(TrainCall& c) {
@@ -972,11 +1000,15 @@ static void dump_chain_timing(const mfas_population* p) {
 }
 #endif
 
-extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train, const mfas_table* dev,
-                                     const int32_t* order, const float* step_scalars, int32_t epochs,
-                                     int64_t max_steps, int32_t snapshot_best, mfas_epoch_stats* stats,
-                                     int32_t* status) {
+// The loop of mfas_population_train and mfas_population_train_from: epochs [first, last) of a schedule of `epochs` epochs.
+// segment = false is mfas_population_train (first = 0, last = epochs, the record is reset); segment = true keeps the progress record,
+// and with first > 0 goes on from the state the previous segment left instead of from a fresh optimizer.
+static int train_impl(mfas_population* p, const mfas_table* train, const mfas_table* dev, const int32_t* order, const float* step_scalars,
+                      int32_t epochs, int64_t max_steps, int32_t snapshot_best, mfas_epoch_stats* stats, int32_t* status,
+                      const int32_t first, const int32_t last, const bool segment) {
     if (!p || !step_scalars || epochs <= 0 || !stats) return fail(MFAS_EINVAL, "bad argument");
+    if (first < 0 || last <= first || last > epochs)
+        return fail(MFAS_EINVAL, "train_from: epochs [" + std::to_string(first) + ", " + std::to_string(last) + ") are no segment of a schedule of " + std::to_string(epochs));
     int rc = check_table(p, train, p->plan.g.multitask);
     if (rc) return rc;
     const bool do_dev = max_steps < 0;
@@ -990,6 +1022,19 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
         return fail(MFAS_EINVAL, "this population was created for 16-bit feature tables (mfas_hyper.tap_bits = 16); f32 tables need tap_bits = 32 or 0");
     if (N - (nb - 1) * B == 1 && g.bn)   // torch BatchNorm1d raises on a size-1 train batch
         return fail(MFAS_EINVAL, "final train batch of size 1 with batchnorm (reference raises ValueError)");
+    const bool resume = first > 0;
+    if (resume)      // nothing has been touched yet: a refused segment leaves the population as it was
+        for (int k = 0; k < K; ++k) {
+            const mfas_population::Progress& pr = p->prog;
+            if (pr.done[k] != first || pr.nb[k] != nb)
+                return fail(MFAS_EINVAL, "train_from: first_epoch = " + std::to_string(first) + " of a schedule with " + std::to_string(nb) +
+                                         " batches per epoch, but candidate " + std::to_string(k) + "'s progress record says " + std::to_string(pr.done[k]) +
+                                         " epoch(s) complete of a schedule with " + std::to_string(pr.nb[k]) + " batches per epoch");
+            if ((pr.keeps_best[k] != 0) != (snapshot_best != 0) || (snapshot_best && !p->best))
+                return fail(MFAS_EINVAL, "train_from: snapshot_best = " + std::to_string(snapshot_best != 0) + " at first_epoch = " + std::to_string(first) +
+                                         ", but candidate " + std::to_string(k) + "'s schedule was started with snapshot_best = " + std::to_string(pr.keeps_best[k]));
+        }
+    if (!segment) p->prog.reset(K, p->best_threshold);      // a plain train() call owes nothing to an earlier schedule
 
     if (p->stats_cap < K * epochs) {
         hipFree(p->d_stats); p->d_stats = nullptr;
@@ -997,20 +1042,22 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
         p->stats_cap = K * epochs;
     }
     HIPCHK(hipMemsetAsync(p->d_stats, 0, sizeof(DevStats) * K * epochs, p->stream));
-    HIPCHK(hipMemsetAsync(p->d_status, 0, sizeof(int32_t) * K, p->stream));
+    if (!resume) HIPCHK(hipMemsetAsync(p->d_status, 0, sizeof(int32_t) * K, p->stream));      // (sticky across the segments of a schedule)
 #ifdef MFAS_CHAIN_TIMING
     HIPCHK(hipMemsetAsync(p->d_status + 64 + 27, 0, sizeof(int32_t), p->stream));
     HIPCHK(hipMemsetAsync(p->d_status + 128, 0, 16 * sizeof(int32_t), p->stream));
     HIPCHK(hipMemsetAsync(p->d_status + 64 + 28, 0xFF, sizeof(int32_t), p->stream));
 #endif
     // every call is a freshly built torch.optim.Adam (ntu_searchable.py:65; main_found_ntu.py:108,128): zero exp_avg / exp_avg_sq
-    HIPCHK(hipMemsetAsync(p->plane + p->plan.plane_stride, 0, sizeof(float) * 2 * (size_t)p->plan.plane_stride, p->stream));
+    // (a segment that goes on finds the optimizer's state where the previous one left it)
+    if (!resume) HIPCHK(hipMemsetAsync(p->plane + p->plan.plane_stride, 0, sizeof(float) * 2 * (size_t)p->plan.plane_stride, p->stream));
     if (snapshot_best && !p->best) HIPCHK(hipMalloc(&p->best, sizeof(float) * (size_t)p->plan.plane_stride));
     // best_model_sd starts as a copy of the INITIAL state_dict (train_searchable/ntu.py:17) and is what the model is
     // left with if no epoch's dev metric beats the starting threshold (0 for accuracy, init_f1 for F1)
-    if (snapshot_best && max_steps < 0)
+    if (snapshot_best && max_steps < 0 && !resume)
         HIPCHK(hipMemcpyAsync(p->best, p->plane, sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, p->stream));
     std::vector<double> best_acc(K, p->best_threshold);
+    if (resume) best_acc = p->prog.best_metric;
     const double metric_scale = g.loss_mode == 1 ? 1.0 / 4294967296.0 : 1.0;   // F1 sums are 32.32 fixed point
     std::vector<DevStats> hstats((size_t)K * epochs);
 
@@ -1024,6 +1071,7 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
     c.aborts.assign(epochs, 0u);
     std::vector<uint32_t>& aborts = c.aborts;
     HIPCHK(init_args(c));
+    HIPCHK(seed_cellflags(c, first));
     p->prof_launches = 0; p->prof_ms = 0.0; p->prof_bytes = 0.0;
     HIPCHK(setup_gather(c));
     if (p->plan.persist) {   // the step scalars live on the device: the kernel walks the steps itself
@@ -1038,7 +1086,7 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
     }
 
     int64_t done = 0;   // train steps completed (max_steps bookkeeping)
-    for (int ep = 0; ep < epochs; ++ep) {
+    for (int ep = first; ep < last; ++ep) {
         int64_t T = nb;
         if (max_steps >= 0) T = std::min<int64_t>(nb, max_steps - done);
         if (T <= 0) break;
@@ -1052,6 +1100,7 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
                 rc = persist_fallback(p);
                 if (rc) return rc;
                 HIPCHK(init_args(c));
+                HIPCHK(seed_cellflags(c, ep));
                 HIPCHK(setup_gather(c));
                 aborts[ep] = 0;
             } else if (aborts[ep]) {
@@ -1101,7 +1150,7 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
             }
         }
     }
-    if (snapshot_best && do_dev) {   // model.load_state_dict(best_model_sd) (:86), unconditionally
+    if (snapshot_best && do_dev && last == epochs) {   // model.load_state_dict(best_model_sd) (:86), unconditionally — once the schedule is complete
         HIPCHK(hipMemcpyAsync(p->plane, p->best, sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, p->stream));
         // the transposed OUT / HEAD tiles the backward chain reads still hold the last epoch's weights: re-derive them
         PackArgs pa = pack_args(p, PK_WT, 0, nullptr);
@@ -1126,6 +1175,13 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
         stats[i].dev_corrects = hstats[i].dev_corr;
     }
     if (status) memcpy(status, hstatus.data(), sizeof(int32_t) * K);
+    if (segment) {      // the record: where the schedule stands, and best_acc (train_searchable/ntu.py:18,82-83) so far
+        for (int k = 0; k < K; ++k) {
+            for (int ep = first; ep < last && !snapshot_best; ++ep)      // (snapshot_best has kept best_acc up to date epoch by epoch)
+                best_acc[k] = std::max(best_acc[k], (double)hstats[(size_t)k * epochs + ep].dev_corr * metric_scale / (double)dev->N);
+            p->prog.done[k] = last; p->prog.nb[k] = nb; p->prog.best_metric[k] = best_acc[k]; p->prog.keeps_best[k] = snapshot_best ? 1 : 0;
+        }
+    }
 #ifdef MFAS_CHAIN_TIMING
     dump_chain_timing(p);
 #endif
@@ -1138,6 +1194,129 @@ extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train
         }
         p->bytes_per_launch = p->prof_launches ? p->prof_bytes / p->prof_launches : 0.0;
     }
+    return MFAS_OK;
+}
+
+extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train, const mfas_table* dev,
+                                     const int32_t* order, const float* step_scalars, int32_t epochs,
+                                     int64_t max_steps, int32_t snapshot_best, mfas_epoch_stats* stats,
+                                     int32_t* status) {
+    return train_impl(p, train, dev, order, step_scalars, epochs, max_steps, snapshot_best, stats, status, 0, epochs, false);
+}
+
+extern "C" int mfas_population_train_from(mfas_population* p, const mfas_table* train, const mfas_table* dev, const int32_t* order,
+                                          const float* step_scalars, int32_t epochs, int32_t first_epoch, int32_t last_epoch,
+                                          int32_t snapshot_best, mfas_epoch_stats* stats, int32_t* status) {
+    return train_impl(p, train, dev, order, step_scalars, epochs, -1, snapshot_best, stats, status, first_epoch, last_epoch, true);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Candidate state in and out of a population: single planes, the progress record, a whole candidate device to device
+// ------------------------------------------------------------------------------------------------
+// flat (state_dict order) -> one plane of candidate k of p; dst_plane / sel as in persist_fallback's move
+static void put_plane(mfas_population* p, int k, float* dst_plane, int sel, int mode, bool with_wt, float* flat, hipStream_t st) {
+    PackArgs b = pack_args(p, mode, sel, flat);
+    b.plane = dst_plane;
+    if (!with_wt) b.wt = nullptr;
+    b.desc = p->d_descs + p->plan.desc_start[k];
+    hipLaunchKernelGGL(k_pack, dim3(p->plan.desc_start[k + 1] - p->plan.desc_start[k]), dim3(256), 0, st, b);
+    hipLaunchKernelGGL(k_vec, dim3(1), dim3(256), 0, st, b, k);
+}
+
+// the kept-best plane of a population that has none yet: every candidate's starts as a copy of its live parameters
+static int ensure_best(mfas_population* p, hipStream_t st) {
+    if (p->best) return MFAS_OK;
+    HIPCHK(hipMalloc(&p->best, sizeof(float) * (size_t)p->plan.plane_stride));
+    HIPCHK(hipMemcpyAsync(p->best, p->plane, sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, st));
+    return MFAS_OK;
+}
+
+extern "C" int mfas_population_set_state(mfas_population* p, int32_t k, int32_t plane, const float* flat) {
+    if (!p || !flat || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad argument");
+    if (plane < 1 || plane > 3)
+        return fail(MFAS_EINVAL, "set_state: plane " + std::to_string(plane) + " (1 = exp_avg, 2 = exp_avg_sq, 3 = kept best; plane 0 is mfas_population_set_params)");
+    HIPCHK(hipSetDevice(p->device));
+    if (plane == 3) {
+        if (int rc = ensure_best(p, p->stream)) return rc;
+        put_plane(p, k, p->best, 0, PK_PUT, false, const_cast<float*>(flat), p->stream);
+        p->prog.keeps_best[k] = 1;
+    } else put_plane(p, k, p->plane, plane, PK_PUT, false, const_cast<float*>(flat), p->stream);
+    HIPCHK(hipGetLastError());
+    return MFAS_OK;
+}
+
+extern "C" int mfas_population_get_progress(mfas_population* p, int32_t k, int64_t* epochs_done, int64_t* nb, double* best_metric,
+                                            int32_t* status) {
+    if (!p || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad argument");
+    if (epochs_done) *epochs_done = p->prog.done[k];
+    if (nb) *nb = p->prog.nb[k];
+    if (best_metric) *best_metric = p->prog.best_metric[k];
+    if (status) {
+        HIPCHK(hipSetDevice(p->device));
+        HIPCHK(hipMemcpyAsync(status, p->d_status + k, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+    }
+    return MFAS_OK;
+}
+
+extern "C" int mfas_population_set_progress(mfas_population* p, int32_t k, const int64_t* epochs_done, const int64_t* nb,
+                                            const double* best_metric, const int32_t* status) {
+    if (!p || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad argument");
+    if ((epochs_done && *epochs_done < 0) || (nb && *nb < 0)) return fail(MFAS_EINVAL, "set_progress: negative epoch or batch count");
+    if (status) {
+        HIPCHK(hipSetDevice(p->device));
+        HIPCHK(hipMemcpyAsync(p->d_status + k, status, sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));      // status is a host word
+    }
+    if (epochs_done) { p->prog.done[k] = *epochs_done; if (*epochs_done == 0) p->prog.keeps_best[k] = 0; }
+    if (nb) p->prog.nb[k] = *nb;
+    if (best_metric) p->prog.best_metric[k] = *best_metric;
+    return MFAS_OK;
+}
+
+extern "C" int mfas_population_move(mfas_population* dst, int32_t kd, mfas_population* src, int32_t ks) {
+    if (!dst || !src || kd < 0 || kd >= dst->K || ks < 0 || ks >= src->K) return fail(MFAS_EINVAL, "bad argument");
+    if (dst->device != src->device) return fail(MFAS_EINVAL, "move: the two populations live on different devices");
+    const mfas_hyper &hd = dst->hp, &hs = src->hp;
+    if (hd.R != hs.R || hd.C != hs.C || (hd.bn != 0) != (hs.bn != 0) || (hd.alphas != 0) != (hs.alphas != 0) ||
+        memcmp(hd.s_sizes, hs.s_sizes, sizeof(hd.s_sizes)) || memcmp(hd.v_sizes, hs.v_sizes, sizeof(hd.v_sizes)))
+        return fail(MFAS_EINVAL, "move: the two populations' hyper-parameters (R, C, bn, alphas, tap widths) differ");
+    const CandDev &cd = dst->plan.cands[kd], &cs = src->plan.cands[ks];
+    bool same = cd.L == cs.L;
+    for (int i = 0; same && i < cd.L; ++i)
+        for (int j = 0; j < 3; ++j) same = same && cd.conf[i][j] == cs.conf[i][j];
+    if (!same || dst->plan.nparams[kd] != src->plan.nparams[ks])
+        return fail(MFAS_EINVAL, "move: candidate " + std::to_string(ks) + " of the source and slot " + std::to_string(kd) + " of the destination have different configurations");
+    HIPCHK(hipSetDevice(dst->device));
+    const int64_t n = src->plan.nparams[ks];
+    if (dst->move_cap < n) {
+        HIPCHK(hipStreamSynchronize(dst->stream));      // (an earlier move may still read the scratch)
+        hipFree(dst->d_move); dst->d_move = nullptr; dst->move_cap = 0;
+        HIPCHK(hipMalloc(&dst->d_move, sizeof(float) * (size_t)n));
+        dst->move_cap = n;
+    }
+    const bool with_best = src->best && src->prog.keeps_best[ks];
+    if (with_best) if (int rc = ensure_best(dst, dst->stream)) return rc;
+    if (src->stream != dst->stream) HIPCHK(hipStreamSynchronize(src->stream));      // what src trained is in memory
+    hipStream_t st = dst->stream;
+    float* flat = dst->d_move;
+    auto carry = [&](float* src_plane, int src_sel, float* dst_plane, int dst_sel, int mode, bool with_wt) {
+        PackArgs a = pack_args(src, PK_GET, src_sel, flat);
+        a.plane = src_plane;
+        a.desc = src->d_descs + src->plan.desc_start[ks];
+        hipMemsetAsync(flat, 0, sizeof(float) * (size_t)n, st);
+        hipLaunchKernelGGL(k_pack, dim3(src->plan.desc_start[ks + 1] - src->plan.desc_start[ks]), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_vec, dim3(1), dim3(256), 0, st, a, ks);
+        put_plane(dst, kd, dst_plane, dst_sel, mode, with_wt, flat, st);
+    };
+    carry(src->plane, 0, dst->plane, 0, PK_SET, true);          // W + BatchNorm running statistics (+ the transposed OUT / HEAD images); zeroes m / v
+    carry(src->plane, 1, dst->plane, 1, PK_PUT, false);         // Adam first moment
+    carry(src->plane, 2, dst->plane, 2, PK_PUT, false);         // Adam second moment
+    if (with_best) carry(src->best, 0, dst->best, 0, PK_PUT, false);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(dst->d_status + kd, src->d_status + ks, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    dst->prog.done[kd] = src->prog.done[ks]; dst->prog.nb[kd] = src->prog.nb[ks];
+    dst->prog.best_metric[kd] = src->prog.best_metric[ks]; dst->prog.keeps_best[kd] = with_best ? 1 : 0;
     return MFAS_OK;
 }
 

@@ -358,9 +358,21 @@ class Population:
             _lib.check(self.lib.mfas_population_init_torch_streams(self._h, s.ctypes.data, b.ctypes.data, float(alpha_mean), float(alpha_std)))
 
     def train(self, train: FeatureTable, dev: Optional[FeatureTable], epochs: int, etas: np.ndarray,
-              order: Optional[torch.Tensor] = None, max_steps: int = -1, snapshot_best: bool = False):
+              order: Optional[torch.Tensor] = None, max_steps: int = -1, snapshot_best: bool = False,
+              first_epoch: int = 0, last_epoch: Optional[int] = None):
         """Runs train_ntu_track_acc for the whole population.  Returns (stats, status): stats is a
-        structured array [K, epochs] with train_loss_sum, dev_loss_sum, train_corrects, dev_corrects."""
+        structured array [K, epochs] with train_loss_sum, dev_loss_sum, train_corrects, dev_corrects.
+        first_epoch / last_epoch: run only epochs [first_epoch, last_epoch) of the `epochs`-epoch schedule
+        (mfas_population_train_from): etas and order stay those of the whole schedule, the statistics columns outside the segment
+        are zero, and a segment that does not start at 0 goes on from the Adam moments, best-epoch bookkeeping and status the
+        previous segment (or import_candidate / move_from) left.  The defaults are the one-call mfas_population_train."""
+        segment = first_epoch != 0 or last_epoch is not None
+        if segment:
+            last_epoch = epochs if last_epoch is None else int(last_epoch)
+            if max_steps >= 0:
+                raise ValueError("max_steps belongs to the one-call train(); a segment is cut at epoch boundaries")
+            if dev is None:
+                raise ValueError("a segment [first_epoch, last_epoch) evaluates dev after every epoch: dev table missing")
         nb = -(-len(train) // self.hp.B)
         etas = np.asarray(etas, np.float64)
         if len(etas) < epochs * nb and max_steps < 0:
@@ -383,11 +395,75 @@ class Population:
         tt = train.to_c()
         td = dev.to_c() if dev is not None else None
         with torch.cuda.device(self._idx):
+            if segment:
+                _lib.check(self.lib.mfas_population_train_from(
+                    self._h, C.byref(tt), C.byref(td), None if order is None else C.c_void_p(order.data_ptr()), sc.ctypes.data,
+                    int(epochs), int(first_epoch), int(last_epoch), int(snapshot_best), stats.ctypes.data, status.ctypes.data))
+                return stats, status
             _lib.check(self.lib.mfas_population_train(
                 self._h, C.byref(tt), C.byref(td) if td is not None else None,
                 None if order is None else C.c_void_p(order.data_ptr()), sc.ctypes.data, int(epochs),
                 int(max_steps), int(snapshot_best), stats.ctypes.data, status.ctypes.data))
         return stats, status
+
+    # ---- resume: the state a candidate carries between segments, populations and files (mfas_population_set_state / _progress / _move)
+    def set_state(self, k: int, plane: int, flat: torch.Tensor, sync: bool = True):
+        """Write ONE plane of candidate k from a flat vector in state_dict order and touch nothing else: 1 = Adam exp_avg,
+        2 = exp_avg_sq, 3 = the kept best-epoch parameters.  (Plane 0 is set_params.)"""
+        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
+        assert flat.numel() == self.param_count(k), (flat.numel(), self.param_count(k))
+        with torch.cuda.device(self._idx):
+            _lib.check(self.lib.mfas_population_set_state(self._h, int(k), int(plane), C.c_void_p(flat.data_ptr())))
+        if sync:
+            torch.cuda.current_stream(self._idx).synchronize()
+
+    def get_progress(self, k: int) -> Dict[str, float]:
+        """Candidate k's progress record: epochs of the current schedule that are complete, that schedule's batches per epoch, the
+        best dev metric so far (train_searchable/ntu.py:18,82-83) and the non-finite-loss status."""
+        ep, nb, bm, st = C.c_int64(0), C.c_int64(0), C.c_double(0.0), C.c_int32(0)
+        with torch.cuda.device(self._idx):
+            _lib.check(self.lib.mfas_population_get_progress(self._h, int(k), C.byref(ep), C.byref(nb), C.byref(bm), C.byref(st)))
+        return {"epochs_done": int(ep.value), "nb": int(nb.value), "best_metric": float(bm.value), "status": int(st.value)}
+
+    def set_progress(self, k: int, epochs_done: int, nb: int, best_metric: float, status: int):
+        ep, n, bm, st = C.c_int64(int(epochs_done)), C.c_int64(int(nb)), C.c_double(float(best_metric)), C.c_int32(int(status))
+        with torch.cuda.device(self._idx):
+            _lib.check(self.lib.mfas_population_set_progress(self._h, int(k), C.byref(ep), C.byref(n), C.byref(bm), C.byref(st)))
+
+    def export_candidate(self, k: int) -> Dict[str, object]:
+        """Everything candidate k needs to go on training elsewhere, as flat device tensors in state_dict order plus its progress:
+        W (with the BatchNorm running statistics), the Adam moments m / v, the kept best-epoch parameters (None when the schedule
+        so far ran without snapshot_best).  The dropout seed belongs to the slot, not to the state."""
+        st: Dict[str, object] = {"W": self.get_params(k, 0), "m": self.get_params(k, 1), "v": self.get_params(k, 2)}
+        st.update(self.get_progress(k))
+        # (plane 3 of a candidate that keeps no best-epoch parameters is refused with MFAS_EINVAL: that is the "None" case)
+        best = torch.empty(self.param_count(k), dtype=torch.float32, device=self.device)
+        rc = self.lib.mfas_population_get_params(self._h, int(k), 3, C.c_void_p(best.data_ptr()))
+        if rc not in (0, -1):
+            _lib.check(rc)
+        st["best"] = best if rc == 0 else None
+        return st
+
+    def import_candidate(self, k: int, state: Dict[str, object]):
+        """Load what export_candidate returned into slot k (same configuration and Hyper): a following
+        train(..., first_epoch=state["epochs_done"]) continues bit for bit."""
+        n = self.param_count(k)
+        for key in ("W", "m", "v"):
+            if state[key].numel() != n:
+                raise ValueError(f"import_candidate: '{key}' holds {state[key].numel()} values, candidate {k} has {n} parameters")
+        self.set_params(k, state["W"], sync=False)       # (zeroes the moments: they follow)
+        self.set_state(k, 1, state["m"], sync=False)
+        self.set_state(k, 2, state["v"], sync=False)
+        if state.get("best") is not None:
+            self.set_state(k, 3, state["best"], sync=False)
+        self.set_progress(k, state["epochs_done"], state["nb"], state["best_metric"], state["status"])
+        torch.cuda.current_stream(self._idx).synchronize()
+
+    def move_from(self, src: "Population", ks: int, kd: int):
+        """Candidate ks of `src` into slot kd of this population, device to device (mfas_population_move): parameters, moments,
+        kept best, BatchNorm statistics, progress and status.  The two layouts may differ; the configurations may not."""
+        with torch.cuda.device(self._idx):
+            _lib.check(self.lib.mfas_population_move(self._h, int(kd), src._h, int(ks)))
 
     def forward(self, k: int, table: FeatureTable, row0: int = 0, nrows: Optional[int] = None,
                 count: bool = False):
@@ -454,6 +530,32 @@ class Population:
         n, ms, by = C.c_int64(0), C.c_double(0), C.c_double(0)
         _lib.check(self.lib.mfas_population_sweep_profile(self._h, C.byref(n), C.byref(ms), C.byref(by)))
         return int(n.value), float(ms.value), float(by.value)
+
+
+def save_checkpoint(path: str, pop: Population):
+    """torch.save of every candidate's export_candidate() state (host tensors) with the configurations and the Hyper."""
+    import dataclasses
+    cands = []
+    for k in range(pop.K):
+        st = pop.export_candidate(k)
+        cands.append({key: (v.cpu() if torch.is_tensor(v) else v) for key, v in st.items()})
+    hyper = {key: (list(v) if isinstance(v, (tuple, list)) else v) for key, v in dataclasses.asdict(pop.hp).items()}
+    torch.save({"format": 1, "hyper": hyper, "confs": [c.tolist() for c in pop.confs], "candidates": cands}, path)
+
+
+def load_checkpoint(path: str, pop: Population):
+    """Load a save_checkpoint file into `pop`; a file written for other configurations or another Hyper is refused."""
+    import dataclasses
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    mine = {key: (list(v) if isinstance(v, (tuple, list)) else v) for key, v in dataclasses.asdict(pop.hp).items()}
+    diff = sorted(key for key in set(mine) | set(ck["hyper"]) if mine.get(key) != ck["hyper"].get(key))
+    if diff:
+        raise ValueError("checkpoint was written for another Hyper: " +
+                         ", ".join(f"{key}={ck['hyper'].get(key)!r} (population: {mine.get(key)!r})" for key in diff))
+    if ck["confs"] != [c.tolist() for c in pop.confs]:
+        raise ValueError(f"checkpoint holds {len(ck['confs'])} candidates with other configurations than this population's {pop.K}")
+    for k, st in enumerate(ck["candidates"]):
+        pop.import_candidate(k, st)
 
 
 F1_FIXED_POINT = float(1 << 32)

@@ -293,6 +293,7 @@ def set_central_states(model, state_dict, using_dataparallel=False):
 
 # ------------------------------------------------------------------------------------------------ the driver
 PROFILE: List[tuple] = []   # (launches, total ms, algorithmic bytes/launch) of k_sweep per call when args.engine_profile
+RUNG_CHANGES: List[tuple] = []   # (candidates before, survivors, seconds) of every rung change of engine_halving calls when args.engine_profile
 
 
 def _require_loader(x, name, device=None) -> FeatureLoader:
@@ -593,6 +594,7 @@ def _train_sampled_models(sampled_configurations, searchable_type, dataloaders, 
                         "(reference behaviour, ntu_searchable.py:86-89)")
     if not train_only_central_params:
         raise NotImplementedError("backbone fine-tuning needs raw video; the engine trains central_params() only")
+    halving = _check_halving(args, return_model)      # args.engine_halving (None: the path below, as ever); refused before anything is created
     device = torch.device(device)
     train_l = _require_loader(dataloaders["train"], "train", device)
     dev_l = _require_loader(dataloaders["dev"], "dev", device)
@@ -631,6 +633,8 @@ def _train_sampled_models(sampled_configurations, searchable_type, dataloaders, 
     models = {}
     sched = LRCosineAnnealingScheduler(args.eta_max, args.eta_min, args.Ti, args.Tm, num_batches_per_epoch)
     etas = sched.eta_table(E * nb)
+    if halving is not None:
+        return _train_halving(halving, confs, searchable_type, train_l, dev_l, args, device, hp, seed_base, etas, premodels, _pos_weight)
     shared_order = {}
     fail_rank = _TEST_FAIL_RANK      # test hook (module attribute, set by tests only): this rank's FIRST share raises (population.train_sharded re-queues it)
     attempts = [0]
@@ -700,6 +704,107 @@ def _train_sampled_models(sampled_configurations, searchable_type, dataloaders, 
         # models live on the rank that trained them; other ranks get None placeholders
         return real_accuracies, [models.get(i) for i in wanted]
     return real_accuracies
+
+
+def _check_halving(args, return_model):
+    """args.engine_halving = (eta, rungs), e.g. (2, (1, 3)): None when unset; refused — before a loader is read or a population
+    created — where the ranking or the survivors' move has nothing to stand on."""
+    halving = getattr(args, "engine_halving", None)
+    if halving is None:
+        return None
+    eta, rungs = int(halving[0]), tuple(int(r) for r in halving[1])
+    E = int(args.epochs)
+    if eta < 2 or not rungs or list(rungs) != sorted(set(rungs)) or rungs[0] < 1 or rungs[-1] >= E:
+        raise ValueError(f"args.engine_halving = (eta, rungs): eta >= 2 and 1 <= rungs[0] < rungs[1] < ... < epochs = {E}; got {halving!r}")
+    if getattr(args, "weightsharing", False):
+        raise NotImplementedError("engine_halving with --weightsharing: candidates that start from the cells earlier candidates "
+                                  "published train one after the other; there is no population to rank")
+    if return_model:
+        raise NotImplementedError("engine_halving with return_model: an eliminated candidate has no fully trained model to return")
+    if popmod.dist_info()[1] > 1:
+        raise NotImplementedError("engine_halving with world > 1: ranking candidates across ranks needs a collective per rung that has "
+                                  "never run on hardware; run the search call on one GPU")
+    return eta, rungs
+
+
+def _train_halving(halving, confs, searchable_type, train_l, dev_l, args, device, hp, seed_base, etas, premodels, _pos_weight):
+    """train_sampled_models with successive halving (args.engine_halving = (eta, rungs), one GPU): every candidate trains epochs
+    [0, rungs[0]); after each rung the candidates are ranked by their best dev metric so far (population.halving_survivors) and the
+    best ceil(K_i / eta) go on to the next rung, the last rung's survivors to the end.  The eta table, the per-candidate sample
+    orders, the initial parameters and the dropout seeds are those of the full schedule by INPUT index, so a survivor trains exactly
+    what it would have trained without halving.  Survivors are regrouped with _plan_rounds — a smaller rung may take another
+    schedule — and carried over with Population.move_from; while a rung changes, the old and the new populations are both alive.
+    An eliminated candidate returns its best dev metric over the epochs it ran (train_searchable/ntu.py:82-83)."""
+    import time
+    eta, rungs = halving
+    K = len(confs)
+    N_tr, N_dev, E = len(train_l.table), len(dev_l.table), int(args.epochs)
+    per_cand = bool(hp.order_per_candidate)
+    chunk_cols = int(getattr(args, "engine_chunk_cols", 0))
+    shared = None if per_cand else make_order(N_tr, E, train_l.shuffle, seed_base + 1, device)
+    dtype = [("train_loss_sum", "f8"), ("dev_loss_sum", "f8"), ("train_corrects", "i8"), ("dev_corrects", "i8")]
+    stats_of = {i: np.zeros(E, dtype) for i in range(K)}
+    status_of = {i: 0 for i in range(K)}
+    ran = {i: 0 for i in range(K)}
+
+    def metric(i):
+        row = stats_of[i][:ran[i]]
+        return best_dev_f1(row, bool(status_of[i]), N_dev) if hp.loss_mode == 1 else best_dev_accuracy(row, N_dev)
+
+    def order_of(group):      # the full schedule's orders of these candidates (a function of the input index, not of the round)
+        return make_order_per_candidate(N_tr, E, train_l.shuffle, seed_base + 1, device, group) if per_cand else shared
+
+    alive = list(range(K))
+    rounds = []        # [(input indices, Population, sample orders)]
+    try:
+        for group, pop in _plan_rounds(hp, confs, alive, device, seed_base, chunk_cols):
+            rounds.append((group, pop, order_of(group)))
+            if _pos_weight is not None:
+                pop.set_pos_weight(_pos_weight)
+            if premodels:
+                for j, i in enumerate(group):
+                    src = premodels[i].module if getattr(args, "use_dataparallel", False) else premodels[i]
+                    m = searchable_type(args, confs[i])
+                    m.load_state_dict(src.state_dict())
+                    pop.set_params(j, m.flat_params())
+            elif getattr(args, "engine_init", "torch") == "device":
+                pop.init([(seed_base + 2 + i) & 0x7FFFFFFF for i in group])
+            elif (not getattr(searchable_type, "_construction_is_standard", False)
+                  or not _init_population_device_streams(pop, args, confs, group, hp, seed_base, device, searchable_type)):
+                _init_population_from_torch(pop, args, confs, group, hp, seed_base, searchable_type, [], {}, device)
+        first = 0
+        for stop in list(rungs) + [E]:
+            for group, pop, order in rounds:
+                stats, status = pop.train(train_l.table, dev_l.table, E, etas, order=order, first_epoch=first, last_epoch=stop)
+                for j, i in enumerate(group):
+                    stats_of[i][first:stop] = stats[j, first:stop]
+                    status_of[i] = int(status[j])
+                    ran[i] = stop
+            if stop == E:
+                break
+            keep = popmod.halving_survivors([metric(i) for i in alive], [status_of[i] for i in alive], eta)
+            alive = [alive[p] for p in keep]
+            where = {i: (pop, j) for group, pop, _ in rounds for j, i in enumerate(group)}
+            old, rounds = rounds, []
+            t_change = time.perf_counter()       # (the last train() call has synchronised its stream)
+            try:
+                for group, pop in _plan_rounds(hp, confs, alive, device, seed_base, chunk_cols):
+                    rounds.append((group, pop, order_of(group)))
+                    if _pos_weight is not None:
+                        pop.set_pos_weight(_pos_weight)
+                    for j, i in enumerate(group):
+                        pop.move_from(where[i][0], where[i][1], j)
+                    torch.cuda.current_stream(device).synchronize()
+            finally:
+                for _, pop, _ in old:
+                    pop.close()
+            if getattr(args, "engine_profile", False):
+                RUNG_CHANGES.append((len(where), len(alive), time.perf_counter() - t_change))
+            first = stop
+    finally:
+        for _, pop, _ in rounds:
+            pop.close()
+    return [metric(i) for i in range(K)]
 
 
 def _bump_bn_counters(model, steps):

@@ -480,6 +480,25 @@ def shard_call(confs, hp, world: int, device=None, all_ranks: bool = False):
     return owner, max(counts + [1]), model
 
 
+def halving_survivors(metrics: Sequence[float], status: Sequence[int], eta: int) -> List[int]:
+    """Successive halving's ranking, a pure function: of K candidates the best ceil(K / eta) by dev metric so far go on.  Ties go to
+    the lower input index; a candidate whose status says a non-finite loss was seen (or whose metric is not a number) ranks behind
+    every finite one, again by index.  Returns the survivors' positions in INPUT order (ascending)."""
+    K = len(metrics)
+    if len(status) != K:
+        raise ValueError("halving_survivors: one status per metric")
+    if int(eta) < 2:
+        raise ValueError("halving_survivors: eta >= 2")
+    keep = -(-K // int(eta))
+
+    def key(i):
+        m = float(metrics[i])
+        bad = bool(status[i]) or not np.isfinite(m)
+        return (1, 0.0, i) if bad else (0, -m, i)
+
+    return sorted(sorted(range(K), key=key)[:keep])
+
+
 def conf_digest(confs) -> int:
     """Order-sensitive 62-bit digest of a list of configurations (checked across ranks before sharding)."""
     import hashlib

@@ -1,6 +1,7 @@
 """Small-population sweep: candidates/s of one train_sampled_models-sized job (E epochs over N_train / N_dev) for K candidates on
 one GPU, launch-per-phase schedule (MFAS_PERSIST=0) vs the default policy (persistent resident step loop where it fits), each with its own default unit
-decomposition.  usage: popsweep.py R B bn E K1,K2,... [mixed] [N_train N_dev]   |   popsweep.py wide  (batch-64 rows, see wide_rows)"""
+decomposition.  usage: popsweep.py R B bn E K1,K2,... [mixed] [N_train N_dev]   |   popsweep.py wide  (batch-64 rows, see wide_rows)
+|   popsweep.py halving  (one search call with and without successive halving, see halving_rows)"""
 import os
 import sys
 import time
@@ -52,6 +53,42 @@ def wide_rows():
             print(f"R={R:3d} B={B:2d} K={K:2d}  {name:10s} {us:8.1f} us/step  {K * B / us * 1e6:12.0f} rows/s  {mb:8.1f} MB/step  "
                   f"{mb / us / 8e6 * 1e6:.3f} of 8 TB/s", flush=True)
 
+
+def halving_rows():
+    """usage: popsweep.py halving — seconds per train_sampled_models call at R = 128, B = 16, E = 10 over 10000 / 5600 bf16 rows,
+    conf-4 candidates, K = 16 and 128, without and with args.engine_halving = (2, (1, 3)) (best of two calls each after one warm-up
+    call at K = 16), and what one rung change costs (regrouping + mfas_population_move of the survivors + destroying the old population)."""
+    from types import SimpleNamespace
+    dev = torch.device("cuda:0")
+    conf4 = np.array([[3, 1, 1], [1, 3, 0], [1, 1, 1], [3, 3, 0]])
+    tr = M.FeatureTable.synthetic(10000, 1, dev, torch.bfloat16, snr=0.12)
+    dv = M.FeatureTable.synthetic(5600, 2, dev, torch.bfloat16, snr=0.12)
+    ld = {"train": M.FeatureLoader(tr, 16, shuffle=True), "dev": M.FeatureLoader(dv, 16, shuffle=False)}
+    print("# R=128 B=16 E=10 N=10000/5600 conf 4: K, s/call plain, s/call engine_halving=(2,(1,3)), ratio, rung changes (candidates -> survivors: ms)")
+    for K in (16, 16, 128):
+        out = {}
+        for halving in (None, (2, (1, 3))):
+            args = SimpleNamespace(vid_len=(8, 32), num_outputs=60, drpt=0.5, inner_representation_size=128, batchnorm=True, alphas=False,
+                                   multitask=False, weightsharing=False, batchsize=16, eta_max=1e-3, eta_min=1e-6, Ti=1, Tm=2,
+                                   use_dataparallel=False, verbose=False, epochs=10, engine_halving=halving, engine_profile=True)
+            best = None
+            for rep in range(2):
+                del M.ntu_searchable.RUNG_CHANGES[:]
+                torch.manual_seed(3)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                M.train_sampled_models([conf4] * K, M.Searchable_Skeleton_Image_Net, ld, args, dev)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                best = dt if best is None else min(best, dt)
+            out[halving is not None] = best
+        rc = ", ".join(f"{a} -> {b}: {s * 1e3:.2f} ms" for a, b, s in M.ntu_searchable.RUNG_CHANGES)
+        print(f"K={K:4d}  plain {out[False]:8.3f} s   halving {out[True]:8.3f} s   x{out[False] / out[True]:.2f}   {rc}", flush=True)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "halving":
+    halving_rows()
+    sys.exit(0)
 
 if len(sys.argv) > 1 and sys.argv[1] == "wide":
     wide_rows()
