@@ -14,12 +14,12 @@
 //            dW = x_t^T dy (f32 MFMA) -> Adam(+L2) update of W/m/v in registers -> store -> immediately
 //            use the new W for the NEXT step's forward partial sums (f32 MFMA).  24 B/param/step = the
 //            algorithmic minimum with state in HBM.
-// Source layout (ONE translation unit; this file includes the rest): common.hip.h (device records, helpers, LDS
-// staging), sweep.hip.h (tile_run, sweep_body, sweep_tap_body), chain.hip.h (chain_body, chain_lean, softmax / BCE rows),
-// wide.hip.h (k_chain_wide / k_sweep_wide: the batch walked in tiles, for batch sizes and widths the others cannot hold),
-// eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe), plan.hip.h (host only: the switches, validate_inputs and
-// plan_layout — layout, schedule, LDS budgets and work lists decided before anything is allocated); below: k_step / k_chain, the kernel
-// tables (one function per kernel family: the only place an instantiation is named) and the host C ABI.
+// Source layout (ONE translation unit; this file includes the rest): common.hip.h (device records, helpers, LDS staging), sweep.hip.h
+// (tile_run, sweep_body, sweep_tap_body), chain.hip.h (chain_body, chain_lean, softmax / BCE rows), wide.hip.h (k_chain_wide / k_sweep_wide:
+// the batch walked in tiles), eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe); host only: plan.hip.h (the switches,
+// validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated), launches.hip.h (the
+// launches of an epoch as data), state.hip.h (state in and out, the candidate carry, move, the fallback), train.hip.h (the train call).  Here:
+// k_step / k_chain, the kernel tables (one function per family: the only place an instantiation is named), create / destroy, the C ABI.
 // Dev evaluation is row-parallel (k_eval).  Weights live in a 16x16 tile-major layout that is exactly the
 // MFMA 16x16x4 f32 operand layout, so every W/m/v access is one coalesced 16 B/lane load.
 //
@@ -422,154 +422,6 @@ extern "C" int64_t mfas_population_param_count(const mfas_population* p, int32_t
     return p->plan.nparams[k];
 }
 
-static PackArgs pack_args(mfas_population* p, int mode, int plane, float* flat) {
-    PackArgs a;
-    memset(&a, 0, sizeof(a));
-    a.desc = p->d_descs; a.cands = p->d_cands; a.plane = p->plane; a.plane_stride = p->plan.plane_stride;
-    a.wt = p->wt; a.flat = flat; a.seeds = p->d_seeds; a.mode = mode; a.sel_plane = plane; a.g = p->plan.g;
-    return a;
-}
-
-extern "C" int mfas_population_set_params(mfas_population* p, int32_t k, const float* flat) {
-    if (!p || !flat || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad argument");
-    HIPCHK(hipSetDevice(p->device));
-    PackArgs a = pack_args(p, PK_SET, 0, const_cast<float*>(flat));
-    a.desc = p->d_descs + p->plan.desc_start[k];
-    const int n = p->plan.desc_start[k + 1] - p->plan.desc_start[k];
-    hipLaunchKernelGGL(k_pack, dim3(n), dim3(256), 0, p->stream, a);
-    hipLaunchKernelGGL(k_vec, dim3(1), dim3(256), 0, p->stream, a, (int)k);
-    HIPCHK(hipGetLastError());
-    return MFAS_OK;
-}
-
-extern "C" int mfas_population_get_params(mfas_population* p, int32_t k, int32_t plane, float* flat) {
-    if (!p || !flat || k < 0 || k >= p->K || plane < 0 || plane > 3) return fail(MFAS_EINVAL, "bad argument");
-    if (plane == 3 && !(p->best && p->prog.keeps_best[k]))
-        return fail(MFAS_EINVAL, "plane 3: candidate " + std::to_string(k) + " keeps no best-epoch parameters (no snapshot_best schedule in progress)");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemsetAsync(flat, 0, sizeof(float) * p->plan.nparams[k], p->stream));
-    PackArgs a = pack_args(p, PK_GET, plane == 3 ? 0 : plane, flat);
-    if (plane == 3) a.plane = p->best;      // (a full image of plane 0, BatchNorm running statistics included)
-    a.desc = p->d_descs + p->plan.desc_start[k];
-    const int n = p->plan.desc_start[k + 1] - p->plan.desc_start[k];
-    hipLaunchKernelGGL(k_pack, dim3(n), dim3(256), 0, p->stream, a);
-    hipLaunchKernelGGL(k_vec, dim3(1), dim3(256), 0, p->stream, a, (int)k);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(p->stream));
-    return MFAS_OK;
-}
-
-extern "C" int mfas_population_init(mfas_population* p, const uint32_t* seeds) {
-    if (!p || !seeds) return fail(MFAS_EINVAL, "bad argument");
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpyAsync(p->d_seeds, seeds, sizeof(uint32_t) * p->K, hipMemcpyHostToDevice, p->stream));
-    PackArgs a = pack_args(p, PK_INIT, 0, nullptr);
-    hipLaunchKernelGGL(k_pack, dim3((unsigned)p->plan.descs.size()), dim3(256), 0, p->stream, a);
-    hipLaunchKernelGGL(k_vec, dim3(p->K), dim3(256), 0, p->stream, a, -1);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(p->stream));   // seeds is a host buffer
-    return MFAS_OK;
-}
-
-// torch.manual_seed(seeds[k]) + the module's construction draws for every candidate, on the device (k_mt_uniform, pack.hip.h).
-// bounds: per candidate 2 * (MFAS_MAX_CELLS + 1) floats — per cell {weight bound, bias bound}, then the classifier's — as the host
-// computed them (kaiming_uniform_(a = sqrt 5) / 1 / sqrt(fan_in), nn.Linear.reset_parameters); alphas ~ N(alpha_mean, alpha_std)
-// drawn LAST like Searchable_Skeleton_Image_Net.__init__ does (ntu_searchable.py:202-204), from the stream's next raw outputs with
-// at::normal_distribution<double>'s arithmetic (Box-Muller: r = sqrt(-2 log1p(-u2)), theta = 2 pi u1; the sine sample is cached
-// for the next draw) in host double precision / libm, exactly what torch's CPU path evaluates.
-extern "C" int mfas_population_init_torch_streams(mfas_population* p, const uint64_t* seeds, const float* bounds, double alpha_mean,
-                                                  double alpha_std) {
-    if (!p || !seeds || !bounds) return fail(MFAS_EINVAL, "bad argument");
-    HIPCHK(hipSetDevice(p->device));
-    const int K = p->K, R = p->hp.R, C = p->hp.C, NB = 2 * (MFAS_MAX_CELLS + 1);
-    int64_t maxp = 0;
-    for (int k = 0; k < K; ++k) maxp = std::max(maxp, p->plan.nparams[k]);
-    const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(K, (64LL << 20) / std::max<int64_t>(maxp, 1)));     // <= 256 MB of flat scratch
-    float* flat = nullptr;
-    MtCand* d_mt = nullptr;
-    uint32_t* d_tail = nullptr;
-    auto cleanup = [&]() { hipFree(flat); hipFree(d_mt); hipFree(d_tail); };
-    hipError_t e = hipMalloc(&flat, sizeof(float) * (size_t)maxp * batch);
-    if (e == hipSuccess) e = hipMalloc(&d_mt, sizeof(MtCand) * batch);
-    if (e == hipSuccess) e = hipMalloc(&d_tail, sizeof(uint32_t) * MT_TAIL * batch);
-    if (e != hipSuccess) { cleanup(); return fail(MFAS_ENOMEM, std::string("init_torch_streams: ") + hipGetErrorString(e)); }
-    std::vector<MtCand> mt(batch);
-    std::vector<uint32_t> tails((size_t)MT_TAIL * batch);
-    std::vector<float> alpha((size_t)MFAS_MAX_CELLS * batch);
-    for (int k0 = 0; k0 < K && e == hipSuccess; k0 += batch) {
-        const int nb = std::min(batch, K - k0);
-        for (int j = 0; j < nb; ++j) {
-            const int k = k0 + j;
-            const CandDev& c = p->plan.cands[k];
-            MtCand& m = mt[j];
-            memset(&m, 0, sizeof(m));
-            m.seed = (uint32_t)(seeds[k] & 0xffffffffULL);
-            m.flat_off = (int64_t)j * maxp;
-            int64_t pos = 0;
-            auto seg = [&](int64_t dst, int64_t n, float b) {
-                m.start[m.nseg] = pos; m.dst[m.nseg] = dst; m.lo[m.nseg] = -b; m.hi[m.nseg] = b;
-                pos += n; ++m.nseg;
-            };
-            for (int i = 0; i < c.L; ++i) {
-                seg(c.f_W[i], (int64_t)R * c.K_in[i], bounds[k * NB + 2 * i]);
-                seg(c.f_b[i], R, bounds[k * NB + 2 * i + 1]);
-            }
-            seg(c.f_Wc, (int64_t)C * R, bounds[k * NB + 2 * MFAS_MAX_CELLS]);
-            seg(c.f_bc, C, bounds[k * NB + 2 * MFAS_MAX_CELLS + 1]);
-            m.start[m.nseg] = pos;
-            m.total = pos;
-        }
-        e = hipMemcpyAsync(d_mt, mt.data(), sizeof(MtCand) * nb, hipMemcpyHostToDevice, p->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(flat, 0, sizeof(float) * (size_t)maxp * nb, p->stream);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_mt_uniform, dim3(nb), dim3(256), 0, p->stream, d_mt, flat, d_tail);
-        e = hipMemcpyAsync(tails.data(), d_tail, sizeof(uint32_t) * MT_TAIL * nb, hipMemcpyDeviceToHost, p->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-        if (e != hipSuccess) break;
-        for (int j = 0; j < nb && e == hipSuccess; ++j) {
-            const int k = k0 + j;
-            const CandDev& c = p->plan.cands[k];
-            // BatchNorm defaults (gamma = 1, running_var = 1) and the alphas, then the usual repacking of a flat vector
-            const uint32_t* t = tails.data() + (size_t)j * MT_TAIL;
-            int used = 0;
-            bool cached = false;
-            double cache = 0.0;
-            auto u53 = [&]() {      // uniform_real_distribution<double>: random64() = (first << 32) | second, 53 bits
-                const uint64_t hi = t[used], lo = t[used + 1];
-                used += 2;
-                return (double)(((hi << 32) | lo) & ((1ULL << 53) - 1)) * (1.0 / 9007199254740992.0);
-            };
-            for (int i = 0; i < c.L; ++i) {
-                double z;
-                if (cached) { z = cache; cached = false; }
-                else {
-                    const double u1 = u53(), u2 = u53();
-                    const double r = ::sqrt(-2.0 * ::log1p(-u2)), theta = 2.0 * 3.14159265358979323846 * u1;
-                    cache = r * ::sin(theta);
-                    cached = true;
-                    z = r * ::cos(theta);
-                }
-                alpha[(size_t)j * MFAS_MAX_CELLS + i] = (float)(z * alpha_std + alpha_mean);
-            }
-            float* fk = flat + (int64_t)j * maxp;
-            e = hipMemcpyAsync(fk + c.f_alpha, alpha.data() + (size_t)j * MFAS_MAX_CELLS, sizeof(float) * c.L, hipMemcpyHostToDevice, p->stream);
-            if (e != hipSuccess) break;
-            if (p->hp.bn) {
-                for (int i = 0; i < c.L && e == hipSuccess; ++i) {
-                    hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, p->stream, fk + c.f_bn[i], 1.0f, (int64_t)R);             // gamma
-                    hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, p->stream, fk + c.f_bn[i] + 3 * (int64_t)R, 1.0f, (int64_t)R);   // running_var
-                }
-            }
-            const int rc = mfas_population_set_params(p, k, fk);
-            if (rc) { cleanup(); return rc; }
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);       // the scratch is reused by the next batch
-    }
-    cleanup();
-    if (e != hipSuccess) return fail(MFAS_EHIP, std::string("init_torch_streams: ") + hipGetErrorString(e));
-    return MFAS_OK;
-}
-
 static int check_table(const mfas_population* p, const mfas_table* t, bool need_logits) {
     if (!t || t->N <= 0) return fail(MFAS_EINVAL, "table: null or empty");
     if (p->plan.g.loss_mode == 0 && !t->label) return fail(MFAS_EINVAL, "table: labels missing");
@@ -620,614 +472,37 @@ static hipError_t launch_eval(mfas_population* p, const EvalArgs& a, int ncand, 
     return hipErrorInvalidValue;
 }
 
-// The resident persistent schedule needs every workgroup of its two launches on the GPU at the same time.  When that cannot be
-// had — another process keeps CUs busy for good, the device is CU-masked, a tool serialises the two launches — the roll call fails
-// BEFORE anything of the epoch has run (abort code 2), so the state in memory is that of the last completed epoch: rebuild the
-// population in its launch-per-phase layout, carry W / m / v (+ the best-epoch snapshot) across through the reference's flat
-// parameter order, and go on from the same epoch.  The handle keeps its identity: the two records swap contents.
-static int persist_fallback(mfas_population* p) {
-    const int K = p->K;
-    std::vector<int32_t> confs((size_t)K * 12, 0), ncells(K);
-    std::vector<uint32_t> seeds(K);
-    int64_t maxp = 0;
-    for (int k = 0; k < K; ++k) {
-        const CandDev& c = p->plan.cands[k];
-        ncells[k] = c.L;
-        seeds[k] = c.drop_seed;
-        for (int i = 0; i < c.L; ++i)
-            for (int j = 0; j < 3; ++j) confs[(k * 4 + i) * 3 + j] = c.conf[i][j];
-        maxp = std::max(maxp, p->plan.nparams[k]);
-    }
-    mfas_population* q = nullptr;
-    int rc = create_impl(&p->hp, confs.data(), ncells.data(), seeds.data(), K, p->device, p->stream, p->chunk_cols_req, &q, false, &p->tune);
-    if (rc) return rc;
-    float* flat = nullptr;
-    hipError_t e = hipMalloc(&flat, sizeof(float) * (size_t)maxp);
-    if (e != hipSuccess) { mfas_population_destroy(q); return fail(MFAS_ENOMEM, "persist_fallback: scratch"); }
-    if (p->best && !q->best) {
-        e = hipMalloc(&q->best, sizeof(float) * (size_t)q->plan.plane_stride);
-        if (e == hipSuccess) e = hipMemsetAsync(q->best, 0, sizeof(float) * (size_t)q->plan.plane_stride, p->stream);
-        if (e != hipSuccess) { hipFree(flat); mfas_population_destroy(q); return fail(MFAS_ENOMEM, "persist_fallback: snapshot"); }
-    }
-    auto move = [&](int k, float* src_plane, int src_sel, float* dst_plane, int dst_sel, int mode, bool with_wt) {
-        PackArgs a = pack_args(p, PK_GET, src_sel, flat);
-        a.plane = src_plane;
-        a.desc = p->d_descs + p->plan.desc_start[k];
-        hipMemsetAsync(flat, 0, sizeof(float) * p->plan.nparams[k], p->stream);
-        hipLaunchKernelGGL(k_pack, dim3(p->plan.desc_start[k + 1] - p->plan.desc_start[k]), dim3(256), 0, p->stream, a);
-        hipLaunchKernelGGL(k_vec, dim3(1), dim3(256), 0, p->stream, a, k);
-        PackArgs b = pack_args(q, mode, dst_sel, flat);
-        b.plane = dst_plane;
-        if (!with_wt) b.wt = nullptr;
-        b.desc = q->d_descs + q->plan.desc_start[k];
-        hipLaunchKernelGGL(k_pack, dim3(q->plan.desc_start[k + 1] - q->plan.desc_start[k]), dim3(256), 0, p->stream, b);
-        hipLaunchKernelGGL(k_vec, dim3(1), dim3(256), 0, p->stream, b, k);
-    };
-    for (int k = 0; k < K; ++k) {
-        move(k, p->plane, 0, q->plane, 0, PK_SET, true);        // W (+ transposed OUT / HEAD images), zeroes m / v
-        move(k, p->plane, 1, q->plane, 1, PK_PUT, false);       // Adam first moment
-        move(k, p->plane, 2, q->plane, 2, PK_PUT, false);       // Adam second moment
-        if (p->best) move(k, p->best, 0, q->best, 0, PK_PUT, false);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(q->d_posw, p->d_posw, sizeof(float) * p->plan.g.Cp, hipMemcpyDeviceToDevice, p->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(q->d_status, p->d_status, sizeof(int32_t) * K, hipMemcpyDeviceToDevice, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    hipFree(flat);
-    if (e != hipSuccess) { mfas_population_destroy(q); return fail(MFAS_EHIP, std::string("persist_fallback: ") + hipGetErrorString(e)); }
-    std::swap(q->d_stats, p->d_stats);
-    std::swap(q->stats_cap, p->stats_cap);
-    std::swap(q->d_scal, p->d_scal);
-    std::swap(q->scal_cap, p->scal_cap);
-    q->best_threshold = p->best_threshold;
-    q->prog = p->prog;
-    q->profiling = p->profiling;
-    q->prof_every = p->prof_every;
-    q->ev.swap(p->ev);
-    q->fell_back = 1;
-    std::swap(*p, *q);
-    mfas_population_destroy(q);      // the resident layout
-    return MFAS_OK;
-}
+// The rest of the host side — host-only headers, included like plan.hip.h — and the C ABI over it
+#include "launches.hip.h"
+#include "state.hip.h"
+#include "train.hip.h"
 
-// ------------------------------------------------------------------------------------------------
-// mfas_population_train: the state of one call and the launches of the two schedules over it
-// ------------------------------------------------------------------------------------------------
-struct TrainCall {
-    mfas_population* p = nullptr;
-    const mfas_table* train = nullptr;
-    const int32_t* order = nullptr;
-    const float* step_scalars = nullptr;
-    int epochs = 0, B = 0;
-    int64_t N = 0, nb = 0;              // train rows, batches per epoch
-    AdamC ac;
-    StepArgs st;
-    int NG = 0;                         // candidate groups A/B: every launch pairs the sweep of one group with the chain of the other (k_step)
-    int64_t split_launches[2] = {0, 0}; // chain_split launches of this call per candidate group (exchange parity)
-    size_t ev_used = 0;                 // profiling: events used by this call, algorithmic bytes of each bracketed launch
-    std::vector<double> ev_bytes;
-    int64_t nlaunch = 0;
-    // Gathered rows (sweep.hip.h, gather_body): two-group streaming schedule + per-candidate sample orders.  The rows of batch
-    // t + 1 of group g are gathered by the launch that carries chain(g, t) (t >= 1) — the launch BEFORE sweep(g, t), which stages
-    // them as x_{t+1} and, a step later, as x_t; batches 0 and 1 are gathered by the group's forward-only prologue launch.
-    int64_t Tcur = 0;
-    bool use_gather = false;
-    int64_t g_par_stride = 0, g_cand_stride = 0;
-    std::vector<uint32_t> aborts;       // abort word of every epoch's resident launch
-    int elt() const { return train->dtype == MFAS_DT_F32 ? 4 : 2; }
-};
-
-static hipError_t init_args(TrainCall& c) {     // (again after persist_fallback: the population's buffers and layout have changed)
-    mfas_population* p = c.p;
-    const LayoutPlan& pl = p->plan;
-    const int K = p->K;
-    StepArgs& st = c.st;
-    c.NG = (int)pl.groups.size();
-    Geo g = pl.g;
-    g.order_stride = (p->hp.order_per_candidate && c.order) ? (int64_t)c.epochs * c.N : 0;    // order: [K][epochs][N_train]
-    memset(&st, 0, sizeof(st));
-    st.sa.cands = p->d_cands; st.sa.plane = p->plane; st.sa.plane_stride = pl.plane_stride; st.sa.wt = p->wt;
-    st.sa.stepbuf = p->stepbuf; st.sa.tab = *c.train; st.sa.order = c.order; st.sa.g = g; st.sa.ac = c.ac;
-    st.ca.plane = p->plane; st.ca.plane_stride = pl.plane_stride; st.ca.wt = p->wt; st.ca.stepbuf = p->stepbuf;
-    st.ca.tab = *c.train; st.ca.order = c.order; st.ca.E = c.epochs; st.ca.g = g; st.ca.stats = p->d_stats;
-    st.ca.status = p->d_status; st.ca.ac = c.ac; st.ca.yf_in_lds = pl.yf_in_lds ? 1 : 0; st.ca.pos_w = p->d_posw;
-    st.ca.vec_in_lds = pl.vec_in_lds ? 1 : 0;
-    st.sa.red_cnt = pl.red_in_sweep ? p->d_red_cnt : nullptr;
-    st.ca.yf_reduced = pl.red_in_sweep ? 1 : 0;
-    hipError_t e_ = hipSuccess;
-    if (pl.red_in_sweep) e_ = hipMemsetAsync(p->d_red_cnt, 0, sizeof(uint32_t) * K * MFAS_MAX_CELLS, p->stream);
-    if (e_ == hipSuccess && pl.same_group) e_ = hipMemsetAsync(p->d_cellflag, 0, sizeof(uint32_t) * K * CELLFLAG_STRIDE, p->stream);
-    // chain_split: every piece of both parities "not written" (all-ones words), parity counter back to 0
-    if (e_ == hipSuccess && pl.chain_split) e_ = hipMemsetAsync(p->d_xch, 0xFF, sizeof(float) * (size_t)K * XCH_CAND_FLOATS, p->stream);
-    st.ca.xch = p->d_xch; st.ca.nsplit = pl.chain_split; st.ca.xpar = 0;
-    c.split_launches[0] = c.split_launches[1] = 0;
-    return e_;
-}
-
-// chain_split in the same-group launch counts ARRIVALS on the per-cell flags: every part adds 1 per step and a sweep unit waits for
-// parts * (gstep + 1).  init_args zeroes the flags, which is right for a call that starts at step 0; one that starts at epoch `ep`
-// (a later segment of a schedule, or the launch-per-phase layout taking over mid-call) starts them where steps 0 .. ep * nb - 1
-// would have left them.  (The one-part chain stores its target and needs nothing.)
-static hipError_t seed_cellflags(TrainCall& c, int64_t ep) {
-    mfas_population* p = c.p;
-    if (ep <= 0 || !p->plan.same_group || !p->plan.chain_split) return hipSuccess;
-    return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->d_cellflag), (int)((uint32_t)p->plan.chain_split * (uint32_t)(ep * c.nb)),
-                             (size_t)p->K * CELLFLAG_STRIDE, p->stream);
-}
-
-static hipError_t setup_gather(TrainCall& c) {
-    mfas_population* p = c.p;
-    const Geo& g = c.st.sa.g;
-    c.use_gather = c.NG == 2 && !p->plan.persist && c.order && g.order_stride > 0 && !p->tune.no_gather;
-    if (!c.use_gather) return hipSuccess;
-    int64_t totw = 0;
-    for (int u = 0; u < MFAS_MAX_TAPS; ++u) totw += g.sw[u] + g.vw[u];
-    c.g_par_stride = totw * g.Bp * c.elt();
-    c.g_cand_stride = 2 * c.g_par_stride;
-    const size_t need = (size_t)c.g_cand_stride * p->K;
-    if (p->gather_cap < need) {
-        hipFree(p->d_gather); p->d_gather = nullptr; p->gather_cap = 0;
-        hipError_t e = hipMalloc(&p->d_gather, need);
-        if (e != hipSuccess) { c.use_gather = false; (void)hipGetLastError(); return hipSuccess; }   // an optimisation: train without it
-        p->gather_cap = need;
-    }
-    if (p->tune.gather_verbose) fprintf(stderr, "[gather] on: %d candidates, %.1f MB of gathered rows\n", p->K, (double)need / 1e6);
-    return hipSuccess;
-}
-
-// HIP events around one profiled launch (the pairs are kept in the population and reused by later calls)
-struct ProfBracket {
-    TrainCall& c;
-    const bool on;
-    const double bytes;             // algorithmic HBM bytes of the launch
-    ProfBracket(TrainCall& c_, bool on_, double bytes_) : c(c_), on(on_), bytes(bytes_) {
-        if (!on) return;
-        mfas_population* p = c.p;
-        if (p->ev.size() < c.ev_used + 2) {
-            hipEvent_t e0, e1;
-            hipEventCreate(&e0); hipEventCreate(&e1);
-            p->ev.push_back(e0); p->ev.push_back(e1);
-        }
-        hipEventRecord(p->ev[c.ev_used], p->stream);
-    }
-    ~ProfBracket() {
-        if (!on) return;
-        hipEventRecord(c.p->ev[c.ev_used + 1], c.p->stream);
-        c.ev_used += 2;
-        c.ev_bytes.push_back(bytes);
-    }
-};
-
-// one fused launch: sweep of group gs at step ts (gs < 0: none) + chain of group gc at step tc (gc < 0: none)
-static void step(TrainCall& c, int gs, int upd, int fwd, int64_t ep, int64_t ts, int gc, int64_t tc) {
-    mfas_population* p = c.p;
-    const LayoutPlan& pl = p->plan;
-    StepArgs& st = c.st;
-    const int64_t N = c.N, nb = c.nb;
-    const int B = c.B, MB = pl.g.MB;
-    auto gather_set = [&](GatherArgs& ga, int s, int64_t t) {
-        ga.pos[s] = ep * N + t * B; ga.base[s] = (int)(t * B);
-        ga.nvalid[s] = (int)std::min<int64_t>(B, N - t * B); ga.par[s] = (int)(t & 1);
-    };
-    unsigned nsw = 0, nch = 0;
-    st.ga.nblocks = 0; st.ga.nsets = 0; st.sa.gather = nullptr;
-    if (c.use_gather) {
-        GatherArgs& ga = st.ga;
-        ga.buf = p->d_gather; ga.cand_stride = c.g_cand_stride; ga.par_stride = c.g_par_stride;
-        int gg = -1;
-        if (gs >= 0 && !upd && fwd && ts == 0) {                    // prologue of group gs: batches 0 and 1
-            gg = gs;
-            gather_set(ga, 0, 0); ga.nsets = 1;
-            if (c.Tcur > 1) { gather_set(ga, 1, 1); ga.nsets = 2; }
-        } else if (gc >= 0 && gs >= 0 && tc >= 1 && tc + 1 < c.Tcur) { // chain(gc, tc) rides with a sweep: batch tc + 1 of group gc
-            gg = gc;
-            gather_set(ga, 0, tc + 1); ga.nsets = 1;
-        }
-        if (gg >= 0) { ga.cands = p->d_cands + pl.groups[gg].c0; ga.nblocks = pl.groups[gg].nc; }
-        if (gs >= 0 && upd) {
-            st.sa.gather = p->d_gather; st.sa.g_cand_stride = c.g_cand_stride; st.sa.g_par_stride = c.g_par_stride;
-            st.sa.g_par_t = (int)(ts & 1); st.sa.g_par_n = (int)((ts + 1) & 1);
-        }
-    }
-    if (gs >= 0) {
-        SweepArgs& s = st.sa;
-        s.desc = p->groups[gs].d_descs;
-        s.tdesc = p->groups[gs].d_taps; s.ntap = (int)pl.groups[gs].taps.size();
-        s.do_update = upd; s.do_forward = fwd;
-        s.pos_t = ep * N + ts * B; s.base_t = (int)(ts * B);
-        s.nvalid_t = (int)std::min<int64_t>(B, N - ts * B);
-        const int64_t tn = fwd ? (upd ? ts + 1 : ts) : ts;
-        s.pos_n = ep * N + tn * B; s.base_n = (int)(tn * B);
-        s.nvalid_n = (int)std::min<int64_t>(B, N - tn * B);
-        const int64_t gstep = ep * nb + ts;
-        s.ac.ss = upd ? c.step_scalars[2 * gstep] : 0.f;
-        s.ac.bc2s = upd ? c.step_scalars[2 * gstep + 1] : 1.f;
-        nsw = (unsigned)(pl.groups[gs].descs.size() + pl.groups[gs].taps.size());
-    }
-    if (gc >= 0) {
-        ChainArgs& ca = st.ca;
-        ca.cands = p->d_cands + pl.groups[gc].c0;
-        ca.pos_t = ep * N + tc * B; ca.base_t = (int)(tc * B);
-        ca.nvalid = (int)std::min<int64_t>(B, N - tc * B);
-        const int64_t gstep = ep * nb + tc;
-        ca.gstep = (int)gstep; ca.epoch = (int)ep;
-        ca.ac.ss = c.step_scalars[2 * gstep]; ca.ac.bc2s = c.step_scalars[2 * gstep + 1];
-        nch = (unsigned)pl.groups[gc].nc;
-    }
-    st.nchain = (int)nch;
-    if (gs < 0) { st.sa.ntap = 0; }
-    if (nsw == 0) {   // chain only: the latency-tuned standalone kernel (wide populations: theirs)
-        launch(pl.wide ? wide_chain_kernel() : chain_kernel(MB, pl.lean_chain), nch, pl.lds_chain, p->stream, st.ca);
-        return;
-    }
-    // algorithmic HBM bytes of this group's update+forward sweep: 24 B/param + the batch's taps + labels
-    ProfBracket prof(c, p->profiling && gs >= 0 && upd && fwd && ((c.nlaunch++ % p->prof_every) == 0),
-                     pl.groups[gs].alg_state + pl.groups[gs].alg_feat * c.elt() + 8.0 * B * pl.groups[gs].nc);
-    if (pl.wide) {    // launch per phase only: the sweep of the one group, after its chain's launch
-        launch(wide_sweep_kernel(pl.nontemporal), nsw, pl.lds_step, p->stream, st);
-        return;
-    }
-    const bool same = pl.same_group && gc == gs && upd;      // chain(g, t) and sweep(g, t) in ONE launch, per-cell flags
-    const bool split = pl.chain_split && nch > 0;            // the chain blocks are chain_split parts (two-group launch: no flags, the kernel boundary)
-    if (split) {      // NS parts per candidate, chain blocks = NS * ceil8(candidates)
-        st.ca.ncand = (int)nch; st.ca.xpar = (int)(c.split_launches[gc & 1]++ & 1);
-        st.nchain = pl.chain_split * (int)((nch + 7) & ~7u);
-    }
-    if (same) {       // (NS parts: the per-cell flags count arrivals)
-        st.sa.cellflag = p->d_cellflag; st.ca.cellflag = p->d_cellflag;
-        st.sa.flag_target = st.ca.flag_target = (split ? (uint32_t)pl.chain_split : 1u) * ((uint32_t)st.ca.gstep + 1u);
-        st.sa.flag_status = p->d_status;
-    }
-    // MB == 2: the two-workgroups-per-CU build unless a co-scheduled chain would bound the launch (see SweepU)
-    // (lean chain: the 128-VGPR build spills 8 registers of the element-parallel chain to scratch and is still the faster
-    //  one — R=16, B=20, 50 / 128 / 512 candidates: 47.2 / 99.2 / 418 us per step against 50.5 / 117.4 / 447 for the 2-workgroup build)
-    const bool occ = nch == 0 || pl.groups[gs].alg_state > pl.occ_bytes;
-    const int wpe = MB == 1 || (MB == 2 && (occ || pl.lean_chain)) ? 4 : 2;
-    const StepKernel k = same ? same_kernel(MB, pl.nontemporal, split ? pl.chain_split : 1)
-                       : split ? step_kernel(MB, pl.nontemporal, 4, false, pl.chain_split) : step_kernel(MB, pl.nontemporal, wpe, pl.lean_chain, 1);
-    launch(k, (unsigned)st.nchain + st.ga.nblocks + nsw, split ? pl.lds_split : pl.lds_step, p->stream, st);
-    if (same) { st.sa.cellflag = nullptr; st.ca.cellflag = nullptr; }
-}
-
-// one persistent launch = all train steps of one epoch (persist.hip.h)
-static hipError_t persist_epoch_once(TrainCall& c, int ep, int64_t T) {
-    mfas_population* p = c.p;
-    const LayoutPlan& pl = p->plan;
-    const Geo& g = pl.g;
-    const int K = p->K;
-    // (test_not_resident: -1 in the product library; the MFAS_TEST_HOOKS variant: from this epoch on every roll call "fails" — nothing is launched)
-    if (p->tune.test_not_resident >= 0 && ep >= p->tune.test_not_resident) { c.aborts[ep] = PERSIST_ABORT_NOT_RESIDENT; return hipSuccess; }
-    hipError_t e = hipMemsetAsync(p->d_sync, 0, sizeof(uint32_t) * ((size_t)K * PERSIST_SYNC_STRIDE + 64), p->stream);
-    if (e != hipSuccess) return e;
-    PersistArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.sa = c.st.sa; pa.ca = c.st.ca;
-    pa.sa.desc = p->d_pdescs; pa.sa.tdesc = nullptr; pa.sa.ntap = 0;
-    pa.ca.cands = p->d_cands;
-    pa.nchain = K; pa.nitems = (int)pl.pdescs.size(); pa.nres = pl.nres; pa.res_chain = pl.res_chain ? 1 : 0; pa.res_wide = pl.res_wide ? 1 : 0;
-    pa.res_nu = pl.res_nu; pa.nres_wg = pl.nres_wg; pa.res_buf_words = pl.res_buf_words;
-    pa.T = (int)T; pa.epoch = ep;
-    pa.lose_step = p->tune.test_lose_step;
-    pa.N = c.N; pa.pos0 = (int64_t)ep * c.N;
-    pa.B = c.B; pa.gstep0 = (int)((int64_t)ep * c.nb);
-    pa.scal = p->d_scal; pa.sync = p->d_sync; pa.need = p->d_need; pa.role = p->d_role; pa.trace = p->d_trace;
-    const unsigned grid = (unsigned)(K + pa.nres_wg);
-    if ((int)grid > p->n_cus) return hipErrorInvalidConfiguration;
-    {
-        // algorithmic bytes of the launch: T update+forward sweeps of every candidate
-        ProfBracket prof(c, p->profiling, (double)T * (pl.groups[0].alg_state + pl.groups[0].alg_feat * c.elt() + 8.0 * c.B * K));
-        const int lw = (int)(pl.lds_president / 4) - PERSIST_LDS_WORDS;
-        // the search default — no BatchNorm, no alphas, single-task softmax CE — runs the chain compiled for exactly that (chain_lean PLAIN)
-        // (round 6: and `--batchnorm` alone, /root/reference/main_searchable_ntu.py:48, the chain compiled for exactly THAT — PLAIN = 2)
-        const bool simple = !g.alphas && !g.multitask && g.loss_mode == 0 && !p->tune.no_plain_chain;
-        const bool x16 = c.train->dtype != MFAS_DT_F32;
-        launch(president_kernel(g.MB, x16, x16 && pl.res_wide, pl.res_nu, simple ? (g.bn ? 2 : 1) : 0), grid, pl.lds_president, p->stream, pa, lw);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return hipMemcpyAsync(&c.aborts[ep], p->d_sync + (size_t)K * PERSIST_SYNC_STRIDE, sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream);
-}
-
-    // The launch is only valid when its whole grid is resident at once (roll call, persist.hip.h).  When another process holds
-    // part of the GPU the roll call fails BEFORE anything is modified (abort code 2): wait a little (jittered, so that two
-    // processes that collided do not collide again in lockstep) and launch the epoch again — up to PERSIST_MAX_RELAUNCHES times
-    // (~0.3 s of trying); after that the caller gives the resident schedule up for this population (persist_fallback).
-static hipError_t persist_epoch(TrainCall& c, int ep, int64_t T) {
-    mfas_population* p = c.p;
-    std::vector<uint32_t>& aborts = c.aborts;
-    for (int attempt = 0;; ++attempt) {
-        hipError_t e = persist_epoch_once(c, ep, T);
-        if (e != hipSuccess) return e;
-        e = hipStreamSynchronize(p->stream);
-        if (e != hipSuccess) return e;
-        if (p->tune.persist_verbose >= 2)
-            fprintf(stderr, "[persist] epoch %d attempt %d: abort word %u\n", ep, attempt, aborts[ep]);
-        if (aborts[ep] != PERSIST_ABORT_NOT_RESIDENT || attempt >= PERSIST_MAX_RELAUNCHES || p->tune.test_not_resident >= 0) {
-            if (attempt && p->tune.persist_verbose) fprintf(stderr, "[persist] epoch %d: grid not resident at once, relaunched %d time(s)\n", ep, attempt);
-            return hipSuccess;
-        }
-        if (p->profiling && c.ev_used >= 2) { c.ev_used -= 2; c.ev_bytes.pop_back(); }       // the failed attempt is not a measurement
-        aborts[ep] = 0;
-        std::this_thread::sleep_for(std::chrono::microseconds(200 + (uint64_t)((reinterpret_cast<uintptr_t>(p) >> 6) * 2654435761u % 1800u) + 50u * (attempt % 16)));
-    }
-}
-
-// MFAS_PERSIST_TRACE: the step-phase timestamps of the last resident launch
-static void dump_persist_trace(const mfas_population* p) {
-    unsigned long long tr[256];
-    if (hipMemcpy(tr, p->d_trace, sizeof(tr), hipMemcpyDeviceToHost) != hipSuccess) return;
-    // step 12 of candidate 0: chain published at tr[4*8+3]; per resident unit: saw-flag / compute-done / arrived, relative to it
-    const long long pub = (long long)tr[4 * 8 + 3];
-    fprintf(stderr, "[persist trace step 12, candidate 0 units, ticks after the chain published: saw-flag done arrived]");
-    for (int u = 0; u < 64; ++u)
-        if (tr[64 + u]) fprintf(stderr, " u%d:%lld/%lld/%lld", u, (long long)tr[64 + u] - pub, (long long)tr[128 + u] - pub, (long long)tr[192 + u] - pub);
-    fprintf(stderr, "\n[chain ready for step 13 at +%lld]\n", (long long)tr[5 * 8 + 1] - pub);
-    fprintf(stderr, "[persist trace, 10 ns ticks; per step: chain wait0 ready done published | sweep-unit-0 wait0 ready done arrived]\n");
-    for (int t = 0; t < 8; ++t) {
-        fprintf(stderr, "  step %2d:", t + 8);
-        for (int j = 0; j < 8; ++j) fprintf(stderr, " %lld", (long long)(tr[t * 8 + j] - tr[0]));
-        fprintf(stderr, "\n");
-    }
-}
-
-#ifdef MFAS_CHAIN_TIMING
-static void dump_chain_timing(const mfas_population* p) {
-    int32_t ts[40];
-    if (hipMemcpy(ts, p->d_status + 64, sizeof(ts), hipMemcpyDeviceToHost) != hipSuccess) return;
-    fprintf(stderr, "[chain timing, shader cycles since kernel entry, candidate 0 step 3]");
-    for (int i = 0; i < 13; ++i) fprintf(stderr, " %d", ts[i]);
-    if (p->plan.chain_split) {      // chain_split's extra stamps: forward cell 1 product done | out sent | tail done | fetched;  backward cell 2 the same;  softmax done;  entry staged
-        fprintf(stderr, "  | split:");
-        for (int i = 13; i < 23; ++i) fprintf(stderr, " %d", ts[i]);
-        fprintf(stderr, "  | entry: record here %d, slabs summed %d, vector block in LDS %d", ts[34], ts[35], ts[36]);
-        fprintf(stderr, "  | 10 ns ticks: chain of step 3 %d, end of chain 3 -> entry of chain 4 %d, chain of step 4 %d", ts[24] - ts[23], ts[25] - ts[24], ts[26] - ts[25]);
-        fprintf(stderr, "; end of chain 3 -> first cell-0 unit sees its flag %d -> last sweep unit of the launch ends %d -> entry of chain 4 %d", (int32_t)((uint32_t)ts[28] - (uint32_t)ts[24]), (int32_t)((uint32_t)ts[27] - (uint32_t)ts[28]), (int32_t)((uint32_t)ts[25] - (uint32_t)ts[27]));
-        fprintf(stderr, "; unit (cell 0, S, chunk 0) after the end of chain 3: flag seen %d, dy staged %d, tiles done %d, slab drained %d, arrival counted %d",
-                ts[29] - ts[24], ts[30] - ts[24], ts[31] - ts[24], ts[32] - ts[24], ts[33] - ts[24]);
-        int32_t ue[16];
-        if (hipMemcpy(ue, p->d_status + 128, sizeof(ue), hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "; last unit end after the end of chain 3, per cell [S V OUT HEAD]:");
-            for (int i = 0; i < 16; ++i) fprintf(stderr, "%s%d", (i & 3) ? " " : " | ", ue[i] ? (int32_t)((uint32_t)ue[i] - (uint32_t)ts[24]) : 0);
-        }
-    }
-    fprintf(stderr, "\n");
-    int32_t cs[24];
-    if (hipMemcpy(cs, p->d_status + 96, sizeof(cs), hipMemcpyDeviceToHost) == hipSuccess) {
-        fprintf(stderr, "[chain checksums, candidate 0 global step 0: sums x4, out x4, logits, dlogits, dy x4, d x4]");
-        for (int i = 0; i < 18; ++i) fprintf(stderr, " %08x", (unsigned)cs[i]);
-        fprintf(stderr, "\n");
-    }
-}
-#endif
-
-// The loop of mfas_population_train and mfas_population_train_from: epochs [first, last) of a schedule of `epochs` epochs.
-// segment = false is mfas_population_train (first = 0, last = epochs, the record is reset); segment = true keeps the progress record,
-// and with first > 0 goes on from the state the previous segment left instead of from a fresh optimizer.
-static int train_impl(mfas_population* p, const mfas_table* train, const mfas_table* dev, const int32_t* order, const float* step_scalars,
-                      int32_t epochs, int64_t max_steps, int32_t snapshot_best, mfas_epoch_stats* stats, int32_t* status,
-                      const int32_t first, const int32_t last, const bool segment) {
-    if (!p || !step_scalars || epochs <= 0 || !stats) return fail(MFAS_EINVAL, "bad argument");
-    if (first < 0 || last <= first || last > epochs)
-        return fail(MFAS_EINVAL, "train_from: epochs [" + std::to_string(first) + ", " + std::to_string(last) + ") are no segment of a schedule of " + std::to_string(epochs));
-    int rc = check_table(p, train, p->plan.g.multitask);
-    if (rc) return rc;
-    const bool do_dev = max_steps < 0;
-    if (do_dev) { rc = check_table(p, dev, p->plan.g.multitask); if (rc) return rc; }
+extern "C" int mfas_population_set_params(mfas_population* p, int32_t k, const float* flat) {
+    if (!p || !flat || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad argument");
     HIPCHK(hipSetDevice(p->device));
-    const Geo& g = p->plan.g;
-    const int K = p->K, B = g.B;
-    const int64_t N = train->N;
-    const int64_t nb = (N + B - 1) / B;
-    if (p->plan.persist && p->plan.nres > 0 && p->hp.tap_bits == 16 && train->dtype == MFAS_DT_F32)
-        return fail(MFAS_EINVAL, "this population was created for 16-bit feature tables (mfas_hyper.tap_bits = 16); f32 tables need tap_bits = 32 or 0");
-    if (N - (nb - 1) * B == 1 && g.bn)   // torch BatchNorm1d raises on a size-1 train batch
-        return fail(MFAS_EINVAL, "final train batch of size 1 with batchnorm (reference raises ValueError)");
-    const bool resume = first > 0;
-    if (resume)      // nothing has been touched yet: a refused segment leaves the population as it was
-        for (int k = 0; k < K; ++k) {
-            const mfas_population::Progress& pr = p->prog;
-            if (pr.done[k] != first || pr.nb[k] != nb)
-                return fail(MFAS_EINVAL, "train_from: first_epoch = " + std::to_string(first) + " of a schedule with " + std::to_string(nb) +
-                                         " batches per epoch, but candidate " + std::to_string(k) + "'s progress record says " + std::to_string(pr.done[k]) +
-                                         " epoch(s) complete of a schedule with " + std::to_string(pr.nb[k]) + " batches per epoch");
-            if ((pr.keeps_best[k] != 0) != (snapshot_best != 0) || (snapshot_best && !p->best))
-                return fail(MFAS_EINVAL, "train_from: snapshot_best = " + std::to_string(snapshot_best != 0) + " at first_epoch = " + std::to_string(first) +
-                                         ", but candidate " + std::to_string(k) + "'s schedule was started with snapshot_best = " + std::to_string(pr.keeps_best[k]));
-        }
-    if (!segment) p->prog.reset(K, p->best_threshold);      // a plain train() call owes nothing to an earlier schedule
-
-    if (p->stats_cap < K * epochs) {
-        hipFree(p->d_stats); p->d_stats = nullptr;
-        HIPCHK(hipMalloc(&p->d_stats, sizeof(DevStats) * K * epochs));
-        p->stats_cap = K * epochs;
-    }
-    HIPCHK(hipMemsetAsync(p->d_stats, 0, sizeof(DevStats) * K * epochs, p->stream));
-    if (!resume) HIPCHK(hipMemsetAsync(p->d_status, 0, sizeof(int32_t) * K, p->stream));      // (sticky across the segments of a schedule)
-#ifdef MFAS_CHAIN_TIMING
-    HIPCHK(hipMemsetAsync(p->d_status + 64 + 27, 0, sizeof(int32_t), p->stream));
-    HIPCHK(hipMemsetAsync(p->d_status + 128, 0, 16 * sizeof(int32_t), p->stream));
-    HIPCHK(hipMemsetAsync(p->d_status + 64 + 28, 0xFF, sizeof(int32_t), p->stream));
-#endif
-    // every call is a freshly built torch.optim.Adam (ntu_searchable.py:65; main_found_ntu.py:108,128): zero exp_avg / exp_avg_sq
-    // (a segment that goes on finds the optimizer's state where the previous one left it)
-    if (!resume) HIPCHK(hipMemsetAsync(p->plane + p->plan.plane_stride, 0, sizeof(float) * 2 * (size_t)p->plan.plane_stride, p->stream));
-    if (snapshot_best && !p->best) HIPCHK(hipMalloc(&p->best, sizeof(float) * (size_t)p->plan.plane_stride));
-    // best_model_sd starts as a copy of the INITIAL state_dict (train_searchable/ntu.py:17) and is what the model is
-    // left with if no epoch's dev metric beats the starting threshold (0 for accuracy, init_f1 for F1)
-    if (snapshot_best && max_steps < 0 && !resume)
-        HIPCHK(hipMemcpyAsync(p->best, p->plane, sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, p->stream));
-    std::vector<double> best_acc(K, p->best_threshold);
-    if (resume) best_acc = p->prog.best_metric;
-    const double metric_scale = g.loss_mode == 1 ? 1.0 / 4294967296.0 : 1.0;   // F1 sums are 32.32 fixed point
-    std::vector<DevStats> hstats((size_t)K * epochs);
-
-    RangeGuard call_range("mfas_population_train K=" + std::to_string(K) + " R=" + std::to_string(g.R) + " B=" + std::to_string(B) +
-                          " E=" + std::to_string(epochs) + (p->plan.persist ? " resident" : " launch-per-phase"));
-    const mfas_hyper& hp = p->hp;
-    TrainCall c;
-    c.p = p; c.train = train; c.order = order; c.step_scalars = step_scalars; c.epochs = epochs; c.B = B; c.N = N; c.nb = nb;
-    c.ac.w1 = (float)(1.0 - hp.beta1); c.ac.b2 = (float)hp.beta2; c.ac.w2 = (float)(1.0 - hp.beta2);
-    c.ac.eps = (float)hp.adam_eps; c.ac.wd = (float)hp.wd; c.ac.ss = 0.f; c.ac.bc2s = 1.f;
-    c.aborts.assign(epochs, 0u);
-    std::vector<uint32_t>& aborts = c.aborts;
-    HIPCHK(init_args(c));
-    HIPCHK(seed_cellflags(c, first));
-    p->prof_launches = 0; p->prof_ms = 0.0; p->prof_bytes = 0.0;
-    HIPCHK(setup_gather(c));
-    if (p->plan.persist) {   // the step scalars live on the device: the kernel walks the steps itself
-        const size_t nsc = (size_t)epochs * nb * 2;
-        if (p->scal_cap < nsc) {
-            hipFree(p->d_scal); p->d_scal = nullptr;
-            HIPCHK(hipMalloc(&p->d_scal, sizeof(float) * nsc));
-            p->scal_cap = nsc;
-        }
-        const size_t have = (size_t)(max_steps >= 0 ? std::min<int64_t>(max_steps, (int64_t)epochs * nb) : (int64_t)epochs * nb) * 2;
-        HIPCHK(hipMemcpyAsync(p->d_scal, step_scalars, sizeof(float) * have, hipMemcpyHostToDevice, p->stream));
-    }
-
-    int64_t done = 0;   // train steps completed (max_steps bookkeeping)
-    for (int ep = first; ep < last; ++ep) {
-        int64_t T = nb;
-        if (max_steps >= 0) T = std::min<int64_t>(nb, max_steps - done);
-        if (T <= 0) break;
-        c.Tcur = T;
-        RangeGuard epoch_range("epoch " + std::to_string(ep));
-        if (p->plan.persist) {
-            HIPCHK(persist_epoch(c, ep, T));
-            if (aborts[ep] == PERSIST_ABORT_NOT_RESIDENT) {
-                // every attempt failed its roll call: nothing of this epoch has run.  Train it — and the rest — launch per phase.
-                if (p->tune.persist_verbose) fprintf(stderr, "[persist] epoch %d: the resident grid never became resident; falling back to launch-per-phase\n", ep);
-                rc = persist_fallback(p);
-                if (rc) return rc;
-                HIPCHK(init_args(c));
-                HIPCHK(seed_cellflags(c, ep));
-                HIPCHK(setup_gather(c));
-                aborts[ep] = 0;
-            } else if (aborts[ep]) {
-                HIPCHK(hipStreamSynchronize(p->stream));
-                return fail(MFAS_EHIP, "persistent step loop: a workgroup timed out waiting for its dependency (abort code 1: the epoch was "
-                                       "abandoned half way, this population's parameters are not usable)");
-            }
-        }
-        if (!p->plan.persist) {
-            const int NG = c.NG;
-            for (int gi = 0; gi < NG; ++gi) step(c, gi, 0, 1, ep, 0, -1, 0);   // prologue: forward sums of batch 0
-            if (NG == 1 && p->plan.same_group) {
-                for (int64_t t = 0; t < T; ++t) step(c, 0, 1, (t + 1 < T) ? 1 : 0, ep, t, 0, t);
-            } else if (NG == 1) {
-                for (int64_t t = 0; t < T; ++t) {
-                    step(c, -1, 0, 0, ep, 0, 0, t);
-                    step(c, 0, 1, (t + 1 < T) ? 1 : 0, ep, t, -1, 0);
-                }
-            } else {
-                step(c, -1, 0, 0, ep, 0, 0, 0);   // chain(A, 0)
-                for (int64_t t = 0; t < T; ++t) {
-                    const int fwd = (t + 1 < T) ? 1 : 0;
-                    step(c, 0, 1, fwd, ep, t, 1, t);                       // sweep(A, t)  ||  chain(B, t)
-                    step(c, 1, 1, fwd, ep, t, fwd ? 0 : -1, t + 1);        // sweep(B, t)  ||  chain(A, t+1)
-                }
-            }
-        }
-        done += T;
-        HIPCHK(hipGetLastError());
-        if (do_dev) {
-            EvalArgs ea;
-            memset(&ea, 0, sizeof(ea));
-            ea.cands = p->d_cands; ea.plane = p->plane; ea.tab = *dev; ea.row0 = 0; ea.nrows = dev->N;
-            ea.cand0 = 0; ea.epoch = ep; ea.E = epochs; ea.g = c.st.sa.g; ea.stats = p->d_stats; ea.pos_w = p->d_posw;
-            HIPCHK(launch_eval(p, ea, K, p->stream));
-            if (snapshot_best) {
-                HIPCHK(hipMemcpyAsync(hstats.data(), p->d_stats, sizeof(DevStats) * K * epochs, hipMemcpyDeviceToHost, p->stream));
-                HIPCHK(hipStreamSynchronize(p->stream));
-                for (int k = 0; k < K; ++k) {
-                    const double acc = (double)hstats[(size_t)k * epochs + ep].dev_corr * metric_scale / (double)dev->N;
-                    if (acc > best_acc[k]) {   // strict >, from 0 (train_searchable/ntu.py:82) / init_f1 (mmimdb.py:18)
-                        best_acc[k] = acc;
-                        HIPCHK(hipMemcpyAsync(p->best + p->plan.cand_plane_base[k], p->plane + p->plan.cand_plane_base[k],
-                                              sizeof(float) * p->plan.cand_plane_size[k], hipMemcpyDeviceToDevice, p->stream));
-                    }
-                }
-            }
-        }
-    }
-    if (snapshot_best && do_dev && last == epochs) {   // model.load_state_dict(best_model_sd) (:86), unconditionally — once the schedule is complete
-        HIPCHK(hipMemcpyAsync(p->plane, p->best, sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, p->stream));
-        // the transposed OUT / HEAD tiles the backward chain reads still hold the last epoch's weights: re-derive them
-        PackArgs pa = pack_args(p, PK_WT, 0, nullptr);
-        hipLaunchKernelGGL(k_pack, dim3((unsigned)p->plan.descs.size()), dim3(256), 0, p->stream, pa);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(hstats.data(), p->d_stats, sizeof(DevStats) * K * epochs, hipMemcpyDeviceToHost, p->stream));
-    std::vector<int32_t> hstatus(K, 0);
-    HIPCHK(hipMemcpyAsync(hstatus.data(), p->d_status, sizeof(int32_t) * K, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
+    put_plane(p, k, p->plane, 0, PK_SET, true, flat, p->stream);
     HIPCHK(hipGetLastError());
-    for (uint32_t ab : aborts)
-        if (ab) return fail(MFAS_EHIP, ab == PERSIST_ABORT_NOT_RESIDENT ? "persistent step loop: the grid never became resident (abort code 2)"
-                                                                         : "persistent step loop: a workgroup timed out waiting for its dependency (abort code 1)");
-    for (int32_t sv : hstatus)
-        if (sv == 2) return fail(MFAS_EHIP, "same-group fused launch: a sweep unit timed out waiting for its cell's dy");
-    if (p->d_trace && p->plan.persist) dump_persist_trace(p);
-    for (size_t i = 0; i < hstats.size(); ++i) {
-        stats[i].train_loss_sum = hstats[i].train_loss;
-        stats[i].dev_loss_sum = hstats[i].dev_loss;
-        stats[i].train_corrects = hstats[i].train_corr;
-        stats[i].dev_corrects = hstats[i].dev_corr;
-    }
-    if (status) memcpy(status, hstatus.data(), sizeof(int32_t) * K);
-    if (segment) {      // the record: where the schedule stands, and best_acc (train_searchable/ntu.py:18,82-83) so far
-        for (int k = 0; k < K; ++k) {
-            for (int ep = first; ep < last && !snapshot_best; ++ep)      // (snapshot_best has kept best_acc up to date epoch by epoch)
-                best_acc[k] = std::max(best_acc[k], (double)hstats[(size_t)k * epochs + ep].dev_corr * metric_scale / (double)dev->N);
-            p->prog.done[k] = last; p->prog.nb[k] = nb; p->prog.best_metric[k] = best_acc[k]; p->prog.keeps_best[k] = snapshot_best ? 1 : 0;
-        }
-    }
-#ifdef MFAS_CHAIN_TIMING
-    dump_chain_timing(p);
-#endif
-    if (p->profiling) {
-        for (size_t i = 0; i + 1 < c.ev_used; i += 2) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, p->ev[i], p->ev[i + 1]) == hipSuccess) {
-                p->prof_ms += ms; p->prof_launches++; p->prof_bytes += c.ev_bytes[i / 2];
-            }
-        }
-        p->bytes_per_launch = p->prof_launches ? p->prof_bytes / p->prof_launches : 0.0;
-    }
     return MFAS_OK;
 }
 
-extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train, const mfas_table* dev,
-                                     const int32_t* order, const float* step_scalars, int32_t epochs,
-                                     int64_t max_steps, int32_t snapshot_best, mfas_epoch_stats* stats,
-                                     int32_t* status) {
-    return train_impl(p, train, dev, order, step_scalars, epochs, max_steps, snapshot_best, stats, status, 0, epochs, false);
+extern "C" int mfas_population_get_params(mfas_population* p, int32_t k, int32_t plane, float* flat) {
+    if (!p || !flat || k < 0 || k >= p->K || plane < 0 || plane > 3) return fail(MFAS_EINVAL, "bad argument");
+    if (plane == 3 && !(p->best && p->prog.keeps_best[k]))
+        return fail(MFAS_EINVAL, "plane 3: candidate " + std::to_string(k) + " keeps no best-epoch parameters (no snapshot_best schedule in progress)");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(get_plane(p, k, plane == 3 ? p->best : p->plane, plane == 3 ? 0 : plane, flat, p->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return MFAS_OK;
 }
 
-extern "C" int mfas_population_train_from(mfas_population* p, const mfas_table* train, const mfas_table* dev, const int32_t* order,
-                                          const float* step_scalars, int32_t epochs, int32_t first_epoch, int32_t last_epoch,
-                                          int32_t snapshot_best, mfas_epoch_stats* stats, int32_t* status) {
-    return train_impl(p, train, dev, order, step_scalars, epochs, -1, snapshot_best, stats, status, first_epoch, last_epoch, true);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Candidate state in and out of a population: single planes, the progress record, a whole candidate device to device
-// ------------------------------------------------------------------------------------------------
-// flat (state_dict order) -> one plane of candidate k of p; dst_plane / sel as in persist_fallback's move
-static void put_plane(mfas_population* p, int k, float* dst_plane, int sel, int mode, bool with_wt, float* flat, hipStream_t st) {
-    PackArgs b = pack_args(p, mode, sel, flat);
-    b.plane = dst_plane;
-    if (!with_wt) b.wt = nullptr;
-    b.desc = p->d_descs + p->plan.desc_start[k];
-    hipLaunchKernelGGL(k_pack, dim3(p->plan.desc_start[k + 1] - p->plan.desc_start[k]), dim3(256), 0, st, b);
-    hipLaunchKernelGGL(k_vec, dim3(1), dim3(256), 0, st, b, k);
-}
-
-// the kept-best plane of a population that has none yet: every candidate's starts as a copy of its live parameters
-static int ensure_best(mfas_population* p, hipStream_t st) {
-    if (p->best) return MFAS_OK;
-    HIPCHK(hipMalloc(&p->best, sizeof(float) * (size_t)p->plan.plane_stride));
-    HIPCHK(hipMemcpyAsync(p->best, p->plane, sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, st));
+extern "C" int mfas_population_init(mfas_population* p, const uint32_t* seeds) {
+    if (!p || !seeds) return fail(MFAS_EINVAL, "bad argument");
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipMemcpyAsync(p->d_seeds, seeds, sizeof(uint32_t) * p->K, hipMemcpyHostToDevice, p->stream));
+    run_pack(p, pack_args(p, PK_INIT, 0, nullptr), -1, true, p->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));   // seeds is a host buffer
     return MFAS_OK;
 }
 
@@ -1238,9 +513,9 @@ extern "C" int mfas_population_set_state(mfas_population* p, int32_t k, int32_t 
     HIPCHK(hipSetDevice(p->device));
     if (plane == 3) {
         if (int rc = ensure_best(p, p->stream)) return rc;
-        put_plane(p, k, p->best, 0, PK_PUT, false, const_cast<float*>(flat), p->stream);
+        put_plane(p, k, p->best, 0, PK_PUT, false, flat, p->stream);
         p->prog.keeps_best[k] = 1;
-    } else put_plane(p, k, p->plane, plane, PK_PUT, false, const_cast<float*>(flat), p->stream);
+    } else put_plane(p, k, p->plane, plane, PK_PUT, false, flat, p->stream);
     HIPCHK(hipGetLastError());
     return MFAS_OK;
 }
@@ -1274,50 +549,17 @@ extern "C" int mfas_population_set_progress(mfas_population* p, int32_t k, const
     return MFAS_OK;
 }
 
-extern "C" int mfas_population_move(mfas_population* dst, int32_t kd, mfas_population* src, int32_t ks) {
-    if (!dst || !src || kd < 0 || kd >= dst->K || ks < 0 || ks >= src->K) return fail(MFAS_EINVAL, "bad argument");
-    if (dst->device != src->device) return fail(MFAS_EINVAL, "move: the two populations live on different devices");
-    const mfas_hyper &hd = dst->hp, &hs = src->hp;
-    if (hd.R != hs.R || hd.C != hs.C || (hd.bn != 0) != (hs.bn != 0) || (hd.alphas != 0) != (hs.alphas != 0) ||
-        memcmp(hd.s_sizes, hs.s_sizes, sizeof(hd.s_sizes)) || memcmp(hd.v_sizes, hs.v_sizes, sizeof(hd.v_sizes)))
-        return fail(MFAS_EINVAL, "move: the two populations' hyper-parameters (R, C, bn, alphas, tap widths) differ");
-    const CandDev &cd = dst->plan.cands[kd], &cs = src->plan.cands[ks];
-    bool same = cd.L == cs.L;
-    for (int i = 0; same && i < cd.L; ++i)
-        for (int j = 0; j < 3; ++j) same = same && cd.conf[i][j] == cs.conf[i][j];
-    if (!same || dst->plan.nparams[kd] != src->plan.nparams[ks])
-        return fail(MFAS_EINVAL, "move: candidate " + std::to_string(ks) + " of the source and slot " + std::to_string(kd) + " of the destination have different configurations");
-    HIPCHK(hipSetDevice(dst->device));
-    const int64_t n = src->plan.nparams[ks];
-    if (dst->move_cap < n) {
-        HIPCHK(hipStreamSynchronize(dst->stream));      // (an earlier move may still read the scratch)
-        hipFree(dst->d_move); dst->d_move = nullptr; dst->move_cap = 0;
-        HIPCHK(hipMalloc(&dst->d_move, sizeof(float) * (size_t)n));
-        dst->move_cap = n;
-    }
-    const bool with_best = src->best && src->prog.keeps_best[ks];
-    if (with_best) if (int rc = ensure_best(dst, dst->stream)) return rc;
-    if (src->stream != dst->stream) HIPCHK(hipStreamSynchronize(src->stream));      // what src trained is in memory
-    hipStream_t st = dst->stream;
-    float* flat = dst->d_move;
-    auto carry = [&](float* src_plane, int src_sel, float* dst_plane, int dst_sel, int mode, bool with_wt) {
-        PackArgs a = pack_args(src, PK_GET, src_sel, flat);
-        a.plane = src_plane;
-        a.desc = src->d_descs + src->plan.desc_start[ks];
-        hipMemsetAsync(flat, 0, sizeof(float) * (size_t)n, st);
-        hipLaunchKernelGGL(k_pack, dim3(src->plan.desc_start[ks + 1] - src->plan.desc_start[ks]), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_vec, dim3(1), dim3(256), 0, st, a, ks);
-        put_plane(dst, kd, dst_plane, dst_sel, mode, with_wt, flat, st);
-    };
-    carry(src->plane, 0, dst->plane, 0, PK_SET, true);          // W + BatchNorm running statistics (+ the transposed OUT / HEAD images); zeroes m / v
-    carry(src->plane, 1, dst->plane, 1, PK_PUT, false);         // Adam first moment
-    carry(src->plane, 2, dst->plane, 2, PK_PUT, false);         // Adam second moment
-    if (with_best) carry(src->best, 0, dst->best, 0, PK_PUT, false);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(dst->d_status + kd, src->d_status + ks, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    dst->prog.done[kd] = src->prog.done[ks]; dst->prog.nb[kd] = src->prog.nb[ks];
-    dst->prog.best_metric[kd] = src->prog.best_metric[ks]; dst->prog.keeps_best[kd] = with_best ? 1 : 0;
-    return MFAS_OK;
+extern "C" int mfas_population_train(mfas_population* p, const mfas_table* train, const mfas_table* dev,
+                                     const int32_t* order, const float* step_scalars, int32_t epochs,
+                                     int64_t max_steps, int32_t snapshot_best, mfas_epoch_stats* stats,
+                                     int32_t* status) {
+    return train_impl(p, train, dev, order, step_scalars, epochs, max_steps, snapshot_best, stats, status, 0, epochs, false);
+}
+
+extern "C" int mfas_population_train_from(mfas_population* p, const mfas_table* train, const mfas_table* dev, const int32_t* order,
+                                          const float* step_scalars, int32_t epochs, int32_t first_epoch, int32_t last_epoch,
+                                          int32_t snapshot_best, mfas_epoch_stats* stats, int32_t* status) {
+    return train_impl(p, train, dev, order, step_scalars, epochs, -1, snapshot_best, stats, status, first_epoch, last_epoch, true);
 }
 
 extern "C" int mfas_population_forward(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0,
@@ -1345,77 +587,13 @@ extern "C" int mfas_population_forward(mfas_population* p, int32_t k, const mfas
     return MFAS_OK;
 }
 
-// One batch through candidate k in TRAIN mode: forward only (logits out), or forward + backward of an external loss
-// (dlogits in): then every parameter's Adam first-moment slot receives its exact GRADIENT and nothing else changes — the step
-// runs with beta1 = 0 (m <- m + 1 * (g - m) = g), weight decay 0 and learning rate 0 (w <- w - 0 * m / denom = w).
-static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0, int32_t nrows, int32_t step_index,
-                        float* logits, const float* dlogits) {
-    if (!p || (!logits && !dlogits) || k < 0 || k >= p->K || row0 < 0) return fail(MFAS_EINVAL, "bad argument");
-    int rc = check_table(p, tab, false);
-    if (rc) return rc;
-    const Geo& g = p->plan.g;
-    if (nrows < 1 || nrows > g.B) return fail(MFAS_EINVAL, "train-mode forward: 1 <= rows <= the population's batch size");
-    if (nrows == 1 && g.bn) return fail(MFAS_EINVAL, "train-mode BatchNorm needs more than 1 row (reference: ValueError)");
-    if (row0 + nrows > tab->N) return fail(MFAS_EINVAL, "row range outside the table");
-    HIPCHK(hipSetDevice(p->device));
-    AdamC ac;
-    ac.w1 = 1.0f; ac.b2 = (float)p->hp.beta2; ac.w2 = (float)(1.0 - p->hp.beta2); ac.eps = (float)p->hp.adam_eps; ac.wd = 0.f; ac.ss = 0.f; ac.bc2s = 1.f;
-    StepArgs st;
-    memset(&st, 0, sizeof(st));
-    st.sa.cands = p->d_cands; st.sa.plane = p->plane; st.sa.plane_stride = p->plan.plane_stride; st.sa.wt = p->wt;
-    st.sa.stepbuf = p->stepbuf; st.sa.tab = *tab; st.sa.order = nullptr; st.sa.g = g; st.sa.g.order_stride = 0;
-    st.sa.desc = p->plan.wide ? p->groups[0].d_descs + p->plan.wide_start[k] : p->d_descs + p->plan.desc_start[k];
-    st.sa.tdesc = nullptr; st.sa.ntap = 0;
-    st.sa.do_update = 0; st.sa.do_forward = 1;
-    st.sa.pos_n = row0; st.sa.base_n = (int)row0; st.sa.nvalid_n = nrows;
-    st.sa.pos_t = row0; st.sa.base_t = (int)row0; st.sa.nvalid_t = nrows;
-    st.sa.ac = ac;
-    st.nchain = 0;
-    const LayoutPlan& pl = p->plan;
-    const unsigned nsw = pl.wide ? (unsigned)(pl.wide_start[k + 1] - pl.wide_start[k]) : (unsigned)(pl.desc_start[k + 1] - pl.desc_start[k]);
-    size_t lds_need = pl.lds_step;   // (a population laid out for resident units budgets its streaming LDS without them)
-    if (!pl.wide)
-        for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) lds_need = std::max(lds_need, sweep_unit_lds(g, pl.descs[j]));
-    if (lds_need > 150 * 1024) return fail(MFAS_EINVAL, "train-mode forward: this population's units are too wide for the streaming kernels");
-    const StepKernel sweep_k = pl.wide ? wide_sweep_kernel(false) : step_kernel(g.MB, false, g.MB == 1 ? 4 : 2, false, 1);
-    if (lds_need > pl.lds_step) HIPCHK(set_lds(sweep_k, lds_need));
-    auto sweep = [&]() { launch(sweep_k, nsw, lds_need, p->stream, st); };
-    if (dlogits) {
-        // The gradient lands in the first-moment slot as m <- m + 1 * (g - m): exact only from m = 0 (1 + (1e-9 - 1) cancels to 0),
-        // and a stale second moment would turn the zero-step's 0 * (m / denom) into 0 * inf.  Whatever this handle has trained
-        // before, candidate k's m and v planes start from zero here (the header documents them as scratch after this call).
-        HIPCHK(hipMemsetAsync(p->plane + p->plan.plane_stride + p->plan.cand_plane_base[k], 0, sizeof(float) * (size_t)p->plan.cand_plane_size[k], p->stream));
-        HIPCHK(hipMemsetAsync(p->plane + 2 * p->plan.plane_stride + p->plan.cand_plane_base[k], 0, sizeof(float) * (size_t)p->plan.cand_plane_size[k], p->stream));
-    }
-    // 1. forward partial sums of the batch (no update): the sweep's forward half over this candidate's units
-    sweep();
-    // 2. the chain: batch-statistics BN (running statistics move like in any train-mode forward), dropout stream of step_index;
-    //    forward only: stops at the logits; backward: continues from the caller's dL/dlogits and leaves dy_i for the sweep
-    ChainArgs& c = st.ca;
-    c.cands = p->d_cands + k; c.plane = p->plane; c.plane_stride = p->plan.plane_stride; c.wt = p->wt; c.stepbuf = p->stepbuf;
-    c.tab = *tab; c.order = nullptr; c.pos_t = row0; c.base_t = (int)row0; c.nvalid = nrows;
-    c.gstep = step_index; c.epoch = 0; c.E = 1; c.g = st.sa.g; c.stats = nullptr; c.status = p->d_status;
-    c.yf_in_lds = p->plan.yf_in_lds ? 1 : 0; c.vec_in_lds = p->plan.vec_in_lds ? 1 : 0; c.pos_w = p->d_posw;
-    c.yf_reduced = 0; c.logits_out = dlogits ? nullptr : logits; c.dlogits_in = dlogits; c.ac = ac;
-    launch(pl.wide ? wide_chain_kernel() : chain_kernel(g.MB, pl.lean_chain), 1u, pl.lds_chain, p->stream, st.ca);
-    if (dlogits) {   // 3. dW of every matrix into its m slot (see the header comment); W, v-scaled-by-lr-0 steps leave W as it was
-        st.sa.do_update = 1; st.sa.do_forward = 0;
-        sweep();
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(p->stream));
-    return MFAS_OK;
-}
-
 extern "C" int mfas_population_forward_train(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0, int32_t nrows,
                                              int32_t step_index, float* logits) {
-    if (!logits) return fail(MFAS_EINVAL, "bad argument");
-    return single_batch(p, k, tab, row0, nrows, step_index, logits, nullptr);
+    return single_batch(p, k, tab, row0, nrows, step_index, logits, nullptr);      // (refuses a null logits itself)
 }
 
 extern "C" int mfas_population_backward(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0, int32_t nrows,
                                         int32_t step_index, const float* dlogits) {
-    if (!dlogits) return fail(MFAS_EINVAL, "bad argument");
     return single_batch(p, k, tab, row0, nrows, step_index, nullptr, dlogits);
 }
 

@@ -1116,7 +1116,7 @@ print("DIGEST", hashlib.sha256(stats.tobytes()).hexdigest(), flush=True)
 def test_resident_schedule_falls_back_to_launch_per_phase_when_never_resident(dev, monkeypatch):
     """The resident schedule's two launches must be co-resident; when the roll call keeps failing (another tenant holds CUs for good,
     a CU mask, a tool that serialises launches) nothing of the epoch has run, and train() rebuilds the population in its
-    launch-per-phase layout, carries W / m / v across and goes on (mfas_hip.hip::persist_fallback).  The hook
+    launch-per-phase layout, carries W / m / v across and goes on (state.hip.h::persist_fallback).  The hook
     MFAS_PERSIST_TEST_NOT_RESIDENT=e makes every roll call from epoch e on fail.  On the same unit decomposition (chunk_cols
     fixed, per-segment units) every schedule gives the same bits, so a run that switches after epoch 0 or 1 must equal the run
     that never switches — statistics, parameters and both Adam moments."""
@@ -1161,6 +1161,43 @@ def test_resident_schedule_falls_back_to_launch_per_phase_when_never_resident(de
             for k in range(K):
                 for pl in range(3):
                     assert np.array_equal(planes[k][pl], ref_planes[k][pl]), (snapshot, fail_from, k, pl)
+
+    # The progress record survives the fallback: a schedule run in two segments, [0, 1) then [1, 3), whose SECOND segment falls back
+    # (at its first epoch, or at its second) equals the uninterrupted resident schedule — statistics, planes 0-2, every candidate's record.
+    def run_segments(fail_from, snapshot, cuts):
+        if fail_from is None:
+            monkeypatch.delenv("MFAS_PERSIST_TEST_NOT_RESIDENT", raising=False)
+        else:
+            monkeypatch.setenv("MFAS_PERSIST_TEST_NOT_RESIDENT", str(fail_from))
+        pop = Population(hp, confs, dev, drop_seeds=list(range(70, 70 + K)), chunk_cols=256)
+        assert pop.schedule()["persistent"]
+        pop.init(list(range(1, K + 1)))
+        stats = None
+        for first, last in cuts:
+            seg, status = pop.train(tr, dv, E, etas, order=order, snapshot_best=snapshot, first_epoch=first, last_epoch=last)
+            assert not status.any()
+            assert pop.schedule()["persistent"] == (fail_from is None or last <= fail_from), (fail_from, first, last)
+            if stats is None:
+                stats = seg
+            else:
+                stats[:, first:last] = seg[:, first:last]
+        planes = b"".join(pop.get_params(k, pl).cpu().numpy().tobytes() for k in range(K) for pl in range(3))
+        prog = [pop.get_progress(k) for k in range(K)]
+        record = b"".join(np.array([p["epochs_done"], p["nb"]], np.int64).tobytes() + np.float64(p["best_metric"]).tobytes() +
+                          np.int32(p["status"]).tobytes() for p in prog)
+        pop.close()
+        return stats.tobytes(), planes, record, prog
+
+    for snapshot in (False, True):
+        ref = run_segments(None, snapshot, [(0, E)])
+        assert all(p["epochs_done"] == E and p["nb"] == nb for p in ref[3])
+        plain_stats, plain_planes, _ = run(None, snapshot)        # (and the one-segment schedule is the one-call train)
+        assert ref[0] == plain_stats.tobytes()
+        assert ref[1] == b"".join(plain_planes[k][pl].tobytes() for k in range(K) for pl in range(3))
+        for fail_from in (1, 2):
+            got = run_segments(fail_from, snapshot, [(0, 1), (1, 3)])
+            for what, a, b in zip(("statistics", "planes", "progress"), got, ref):
+                assert a == b, (snapshot, fail_from, what, got[3], ref[3])
 
 
 def test_two_processes_share_the_gpu_with_persistent_grids(dev, tmp_path):
