@@ -54,7 +54,7 @@ TAU_M = G.TAU_GRAD
 TAU_V = G.TAU_GRAD
 TAU_W = 20.0
 TAUS = {"m": TAU_M, "v": 1.0, "w": TAU_W, "runstat": G.TAU_RUNSTAT, "loss": 1.0}
-STEPS = 3
+STEPS = 3      # the steps the tests of this file check: (1, 2, 3)
 EPOCHS = 2
 # parameters, taps and orders of case i are drawn from SEED0 + i.  TAU_RUNSTAT's x4 margin is narrow (the float32 oracle sits at
 # 0.7 .. 0.85 of the allowed 1.0 on every draw); on some draws (2 of the 8 bases tried) one element of one case reaches 1.1 .. 1.2.
@@ -97,21 +97,29 @@ def step_etas(N, B):
     return O.eta_sequence(1e-3, 1e-6, 1, 2, N / B, EPOCHS * nb)
 
 
-def engine_states(pop, tab, p0s, etas, order_t):
-    """S0..S3 of every candidate and the statistics of the 0..3-step calls: the same initial parameters before each call."""
-    S, ST = [], []
-    for j in range(STEPS + 1):
+def train_rows(B, full=1):
+    """Rows of a train table with `full` full batches and the ragged last one."""
+    return full * B + ragged_rows(B)
+
+
+def engine_states(pop, tab, p0s, etas, order_t, steps=(1, 2, 3)):
+    """{j: state of every candidate} and {j: statistics} of the j-step calls, j in {0} | steps | {s - 1 for s in steps}: the same
+    initial parameters before each call."""
+    S, ST = {}, {}
+    for j in sorted({0} | set(steps) | {s - 1 for s in steps}):
         for k, p0 in enumerate(p0s):
             pop.set_state_dict(k, p0)
         stats, status = pop.train(tab, None, EPOCHS, etas, order=order_t, max_steps=j)
         assert not status.any(), (j, status)
-        S.append([{"w": state_np(pop, k, 0), "m": state_np(pop, k, 1), "v": state_np(pop, k, 2)} for k in range(len(p0s))])
-        ST.append(stats.copy())
+        S[j] = [{"w": state_np(pop, k, 0), "m": state_np(pop, k, 1), "v": state_np(pop, k, 2)} for k in range(len(p0s))]
+        ST[j] = stats.copy()
     return S, ST
 
 
-def check_candidate(S, ST, k, conf, hp, p0, t, order_k, seed, etas, tag, rec):
-    """Items 1-6 of one candidate for steps 1..3, and what a 0-step call must leave."""
+def check_candidate(S, ST, k, conf, hp, p0, t, order_k, seed, etas, tag, rec, steps=(1, 2, 3)):
+    """Items 1-6 of one candidate for every step of `steps` (sorted, 1-based global steps), each from the engine's own state
+    after step - 1, and what a 0-step call must leave."""
+    assert tuple(steps) == tuple(sorted(set(steps))) and steps[0] >= 1, steps
     train_keys = O.trainable_keys(conf, hp)
     for key, a in S[0][k]["w"].items():                               # a 0-step call: parameters untouched, moments zero
         if key in p0 and (hp.bn or ".2." not in key):
@@ -120,7 +128,7 @@ def check_candidate(S, ST, k, conf, hp, p0, t, order_k, seed, etas, tag, rec):
         assert all(not S[0][k][pl][key].any() for key in train_keys), (tag, "0 steps", pl)
     assert ST[0][k]["train_loss_sum"].tolist() == [0.0] * EPOCHS and ST[0][k]["train_corrects"].tolist() == [0] * EPOCHS
     pw = pos_weight(hp) if hp.loss_mode == 1 else None
-    for j in range(1, STEPS + 1):
+    for j in steps:
         batch, ep = batch_of(t, order_k, hp.B, j)
         prev, cur = S[j - 1][k], S[j][k]
         exp = R64.train_step64(prev, conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, TAU_V, observed=cur, pos_weight=pw)
@@ -135,9 +143,11 @@ def check_candidate(S, ST, k, conf, hp, p0, t, order_k, seed, etas, tag, rec):
                 assert all(np.array_equal(cur[pl][key], prev[pl][key]) for pl in ("w", "m", "v")), (tag, j, key)
         for e in range(ep + 1, EPOCHS):
             assert ST[j][k]["train_loss_sum"][e] == 0.0, (tag, j, e)
-    # max_steps counts across epochs: the 3-step call ran one step of epoch 1 (C = 1 has loss 0 and every row correct)
-    last = ST[STEPS][k]
-    assert (last["train_loss_sum"][1] != 0.0 or last["train_corrects"][1] != 0) and np.isfinite(last["train_loss_sum"]).all(), (tag, last)
+    # max_steps counts across epochs: the call of the last step ran into the epoch that step lies in (C = 1 has loss 0 and every
+    # row correct)
+    last, ep_last = ST[steps[-1]][k], batch_of(t, order_k, hp.B, steps[-1])[1]
+    assert ep_last >= 1, (tag, steps)
+    assert (last["train_loss_sum"][ep_last] != 0.0 or last["train_corrects"][ep_last] != 0) and np.isfinite(last["train_loss_sum"]).all(), (tag, last)
 
 
 @pytest.mark.gpu
@@ -179,14 +189,10 @@ TRAIN_SCHEDULES.update({
 SCHED_CONFS = ([[3, 3, 0], [1, 2, 1]], [[0, 3, 2]], [[2, 1, 0], [3, 0, 1], [1, 1, 0]], [[1, 0, 1]])
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("order_mode", ["shared", "per_candidate"])
-@pytest.mark.parametrize("name", list(TRAIN_SCHEDULES))
-def test_train_schedules_steps_vs_ref64(dev, name, order_mode):
-    """Every train schedule, asserted with pop.schedule(), K >= 3 candidates of different depth and nonlinearity with their own
-    dropout seeds, a shared or a per-candidate sample order: every candidate's steps 1..3 against ref64."""
-    torch = G._torch()
-    from mfas_amd import Population
+def schedule_inputs(name, order_mode, full=1):
+    """What a TRAIN_SCHEDULES entry trains, as numpy (no device): hyper-parameters, K >= 3 candidates of different depth and
+    nonlinearity with their own dropout seeds and initial parameters, a bf16 train table of `full` full batches and a ragged one,
+    a shared or a per-candidate sample order, the learning rates."""
     from tests.helpers import engine_hyper
     R, C, B, env, cc, K, tap_bits, check = TRAIN_SCHEDULES[name]
     hp = O.Hyper(R=R, C=C, B=B, bn=True, drpt=0.5, s_sizes=W_A["s"], v_sizes=W_A["v"], epochs=EPOCHS)
@@ -195,23 +201,51 @@ def test_train_schedules_steps_vs_ref64(dev, name, order_mode):
     ehp = engine_hyper(hp)
     ehp.tap_bits = tap_bits
     ehp.order_per_candidate = order_mode == "per_candidate"
+    p0s = [O.init_params(c, hp, 40 + k, perturb_bn=True) for k, c in enumerate(confs)]
+    N = train_rows(B, full)
+    t = case_table((name, R, C, B, W_A, None, True, 0.5, ""), hp, N, 61, "bfloat16")
+    order = make_order(N, 7, K if ehp.order_per_candidate else None)
+    return dict(hp=hp, ehp=ehp, confs=confs, seeds=seeds, p0s=p0s, N=N, t=t, dtype="bfloat16", order=order, etas=step_etas(N, B))
+
+
+def schedule_pop(name, inp, dev):
+    """The population of a TRAIN_SCHEDULES entry under the entry's switches, its schedule asserted with pop.schedule()."""
+    from mfas_amd import Population
+    R, C, B, env, cc, K, tap_bits, check = TRAIN_SCHEDULES[name]
     os.environ.update(env)
     try:
-        pop = Population(ehp, confs, dev, drop_seeds=seeds, chunk_cols=cc)
+        pop = Population(inp["ehp"], inp["confs"], dev, drop_seeds=inp["seeds"], chunk_cols=cc)
     finally:
         for key in env:
             os.environ.pop(key, None)
     try:
         sched = pop.schedule()
         assert check(sched), (name, sched)
-        p0s = [O.init_params(c, hp, 40 + k, perturb_bn=True) for k, c in enumerate(confs)]
-        N = B + ragged_rows(B)
-        t = case_table((name, R, C, B, W_A, None, True, 0.5, ""), hp, N, 61, "bfloat16")
-        order = make_order(N, 7, K if ehp.order_per_candidate else None)
-        etas = step_etas(N, B)
-        S, ST = engine_states(pop, gpu_table(t, "bfloat16", dev), p0s, etas, torch.from_numpy(order).to(dev))
+    except BaseException:
+        pop.close()
+        raise
+    return pop
+
+
+def run_schedule(dev, name, order_mode, full, steps, rec):
+    """One TRAIN_SCHEDULES entry: every candidate's `steps` against ref64."""
+    torch = G._torch()
+    inp = schedule_inputs(name, order_mode, full)
+    pop = schedule_pop(name, inp, dev)
+    try:
+        S, ST = engine_states(pop, gpu_table(inp["t"], inp["dtype"], dev), inp["p0s"], inp["etas"], torch.from_numpy(inp["order"]).to(dev), steps)
     finally:
         pop.close()
-    for k, c in enumerate(confs):
-        check_candidate(S, ST, k, c, hp, p0s[k], t, order[k] if ehp.order_per_candidate else order, seeds[k], etas,
-                        f"{name} {order_mode} cand {k}", f"{name}/{order_mode}")
+    per = inp["ehp"].order_per_candidate
+    for k, c in enumerate(inp["confs"]):
+        check_candidate(S, ST, k, c, inp["hp"], inp["p0s"][k], inp["t"], inp["order"][k] if per else inp["order"], inp["seeds"][k],
+                        inp["etas"], f"{name} {order_mode} cand {k}", rec, steps)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order_mode", ["shared", "per_candidate"])
+@pytest.mark.parametrize("name", list(TRAIN_SCHEDULES))
+def test_train_schedules_steps_vs_ref64(dev, name, order_mode):
+    """Every train schedule, asserted with pop.schedule(), K >= 3 candidates of different depth and nonlinearity with their own
+    dropout seeds, a shared or a per-candidate sample order: every candidate's steps 1..3 against ref64."""
+    run_schedule(dev, name, order_mode, 1, (1, 2, 3), f"{name}/{order_mode}")

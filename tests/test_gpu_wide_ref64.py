@@ -133,8 +133,8 @@ def test_cases_were_refused_before():
     assert why["wc"] == why["w512b"] == "C_padded" and all(why[c] == "lds" for c in ("w65", "w80", "w177", "w256", "w512a")), why
 
 
-def setup(case, dev, order_mode="shared"):
-    from mfas_amd import Population
+def case_inputs(case, order_mode="shared"):
+    """What a wide case trains, as numpy (no device): hyper-parameters, the K candidates with their initial parameters and seeds."""
     from tests.helpers import engine_hyper
     hp = G.case_hyper(base_case(case))
     seed = SEED0 + WIDE_IDS.index(case[0])
@@ -146,10 +146,42 @@ def setup(case, dev, order_mode="shared"):
     ehp = engine_hyper(hp)
     ehp.order_per_candidate = order_mode == "per_candidate"
     seeds = [seed + 3 * k for k in range(K)]
+    return hp, ehp, seed, confs, p0s, seeds
+
+
+def train_inputs(case, hp, ehp, seed, full=1):
+    """The train table of `full` full batches and a ragged one, the sample order and the learning rates of a wide case."""
+    N = GT.train_rows(hp.B, full)
+    assert 2 <= N - full * hp.B <= hp.B - 1
+    t = G.case_table(base_case(case), hp, N, seed, case[9])
+    return N, t, GT.make_order(N, seed, K if ehp.order_per_candidate else None), GT.step_etas(N, hp.B)
+
+
+def setup(case, dev, order_mode="shared"):
+    from mfas_amd import Population
+    hp, ehp, seed, confs, p0s, seeds = case_inputs(case, order_mode)
     pop = Population(ehp, confs, dev, drop_seeds=seeds)
     if hp.loss_mode == 1:
         pop.set_pos_weight(G.pos_weight(hp))
     return hp, ehp, seed, confs, p0s, seeds, pop
+
+
+def run_train_steps(dev, case, order_mode, full, steps, rec=None):
+    """train(max_steps = j) of the case's K = 3 candidates, `steps` against ref64 (test_gpu_train_ref64's check) under the case's taus."""
+    torch = G._torch()
+    cid, dtype = case[0], case[9]
+    hp, ehp, seed, confs, p0s, seeds, pop = setup(case, dev, order_mode)
+    try:
+        assert pop.schedule()["wide"] == 1
+        N, t, order, etas = train_inputs(case, hp, ehp, seed, full)
+        S, ST = GT.engine_states(pop, G.gpu_table(t, dtype, dev), p0s, etas, torch.from_numpy(order).to(dev), steps)
+    finally:
+        pop.close()
+    from unittest import mock
+    with mock.patch.dict(GT.TAUS, case_taus(cid)[1]):      # (test_gpu_train_ref64's check reads its module's taus)
+        for k in range(K):
+            GT.check_candidate(S, ST, k, confs[k], hp, p0s[k], t, order[k] if ehp.order_per_candidate else order, seeds[k], etas,
+                               f"{cid} {order_mode} cand {k}", rec or f"wide/{dtype}", steps)
 
 
 @pytest.mark.gpu
@@ -230,24 +262,7 @@ TRAIN_PARAMS = [(c, "shared") for c in WIDE_CASES] + [(c, "per_candidate") for c
 def test_wide_train_steps_vs_ref64(dev, case, order_mode):
     """train(max_steps = 0..3) of K = 3 candidates of different depth, step by step against ref64 (test_gpu_train_ref64's check):
     N = B + ragged rows, so step 1 is a full batch through the sample order, step 2 the ragged last batch, step 3 crosses the epoch."""
-    torch = G._torch()
-    cid, dtype = case[0], case[9]
-    hp, ehp, seed, confs, p0s, seeds, pop = setup(case, dev, order_mode)
-    try:
-        assert pop.schedule()["wide"] == 1
-        N = hp.B + GT.ragged_rows(hp.B)
-        assert 2 <= N - hp.B <= hp.B - 1
-        t = G.case_table(base_case(case), hp, N, seed, dtype)
-        order = GT.make_order(N, seed, K if ehp.order_per_candidate else None)
-        etas = GT.step_etas(N, hp.B)
-        S, ST = GT.engine_states(pop, G.gpu_table(t, dtype, dev), p0s, etas, torch.from_numpy(order).to(dev))
-    finally:
-        pop.close()
-    from unittest import mock
-    with mock.patch.dict(GT.TAUS, case_taus(cid)[1]):      # (test_gpu_train_ref64's check reads its module's taus)
-        for k in range(K):
-            GT.check_candidate(S, ST, k, confs[k], hp, p0s[k], t, order[k] if ehp.order_per_candidate else order, seeds[k], etas,
-                               f"{cid} {order_mode} cand {k}", f"wide/{dtype}")
+    run_train_steps(dev, case, order_mode, 1, (1, 2, 3))
 
 
 @pytest.mark.gpu

@@ -317,27 +317,29 @@ def oracle_step32(st, conf, hp, batch, seed, step, eta, t, pw=None, mut="", stal
     return {"w": P, "m": ad.m, "v": ad.v}, float(loss) * n, count
 
 
-def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False):
-    """Steps 1..3 as test_gpu_train_ref64 sets them up, the float32 oracle checked step by step: worst ratio per quantity."""
-    hp = G.case_hyper(case)
-    seed = GT.SEED0 + G.CASE_IDS.index(case[0]) if seed is None else seed
-    conf, p0 = G.case_params(case, hp, seed)
-    N = hp.B + GT.ragged_rows(hp.B)
-    t = G.case_table(case, hp, N, seed, dtype)
-    order = GT.make_order(N, seed)
-    wrong = GT.make_order(N, seed, 2)[1]            # another candidate's order
-    etas = GT.step_etas(N, hp.B)
+def stale_taps(batch, stale):
+    """`batch` with its tap columns replaced by the first rows of `stale` (labels and logits inputs stay the batch's own)."""
+    n = len(batch["label"])
+    return {k: (stale[k][:n] if k[0] in "sv" and k[1:].isdigit() else v) for k, v in batch.items()}
+
+
+def oracle_steps(conf, hp, p0, t, order, etas, seed, steps, taus, tag, mut="", wrong=None):
+    """The float32 oracle through steps 1..steps[-1] of one candidate (table t, sample order [EPOCHS][N], dropout seed), every
+    step of `steps` checked against ref64 from the oracle's own state before it: worst ratio per quantity."""
+    N = order.shape[1]
     pw = G.pos_weight(hp) if hp.loss_mode == 1 else None
     keys = O.trainable_keys(conf, hp)
     hist = [{"w": p0, "m": {k: np.zeros_like(p0[k]) for k in keys}, "v": {k: np.zeros_like(p0[k]) for k in keys}}]
     worst = {}
     nb = -(-N // hp.B)
-    for j in range(1, GT.STEPS + 1):
+    for j in range(1, steps[-1] + 1):
         batch, ep = GT.batch_of(t, order, hp.B, j)
+        bi = (j - 1) % nb
+        n = len(batch["label"])
         seen, eta_j, t_j, m, stale = batch, etas[j - 1], j, mut, None
-        if mut == "div_B" and len(batch["label"]) == hp.B:
+        if mut == "div_B" and n == hp.B:
             m = ""                                  # (only the ragged batch divides by something else than B)
-        if mut == "bn_pad" and len(batch["label"]) == hp.B:
+        if mut == "bn_pad" and n == hp.B:
             m = ""
         if mut == "scalars_prev" and j >= 2:
             eta_j, t_j = etas[j - 2], j - 1
@@ -347,12 +349,31 @@ def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False):
             seen = GT.batch_of(t, order, hp.B, j - ep * nb)[0]
         if mut == "order_other_candidate":
             seen = GT.batch_of(t, wrong, hp.B, j)[0]
+        if mut == "stage_lag2" and bi >= 2:         # the staging buffer of batch bi was not refilled: it still holds batch bi - 2
+            seen = stale_taps(batch, GT.batch_of(t, order, hp.B, j - 2)[0])
+        if mut == "order_wrap2":                    # the order-table offset wraps after two batches
+            idx = order[ep][(bi % 2) * hp.B:(bi % 2) * hp.B + n]
+            seen = {k: v[idx] for k, v in t.items()}
         new, loss, count = oracle_step32(hist[-1], conf, hp, seen, seed, j - 1, eta_j, t_j, pw, m, stale)
-        exp = R64.train_step64(hist[-1], conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, GT.TAU_V, observed=new, pos_weight=pw)
-        r = R64.check_train_step(exp, new, loss, count, GT.TAUS, f"{case[0]} step {j}", hard=False)
-        worst = {q: max(worst.get(q, 0.0), r[q]) for q in r}
+        if j in steps:
+            exp = R64.train_step64(hist[-1], conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, GT.TAU_V, observed=new, pos_weight=pw)
+            r = R64.check_train_step(exp, new, loss, count, taus, f"{tag} step {j}", hard=False)
+            worst = {q: max(worst.get(q, 0.0), r[q]) for q in r}
         hist.append(new)
     return worst
+
+
+def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False, N=None, steps=(1, 2, 3)):
+    """Steps of train() as test_gpu_train_ref64 sets them up (N rows: by default one full batch and the ragged one), the float32
+    oracle checked step by step on `steps`: worst ratio per quantity."""
+    hp = G.case_hyper(case)
+    seed = GT.SEED0 + G.CASE_IDS.index(case[0]) if seed is None else seed
+    conf, p0 = G.case_params(case, hp, seed)
+    N = GT.train_rows(hp.B) if N is None else N
+    t = G.case_table(case, hp, N, seed, dtype)
+    order = GT.make_order(N, seed)
+    wrong = GT.make_order(N, seed, 2)[1]            # another candidate's order
+    return oracle_steps(conf, hp, p0, t, order, GT.step_etas(N, hp.B), seed, tuple(steps), GT.TAUS, case[0], mut, wrong)
 
 
 def test_train_case_dtypes_rotate():
