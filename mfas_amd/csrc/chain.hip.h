@@ -356,6 +356,28 @@ __device__ __forceinline__ void softmax_rows_lean(const ChainArgs& a, float* lg_
     }
 }
 
+// Two pieces of the general chain's arithmetic that chain_body and chain_split both call (one statement each; the rest of the column
+// arithmetic is transcribed in both and pinned by the parity tests — as shared functions it changed the generated code of every general-
+// chain kernel, profiles/chain_shared_arith_codeobj.log):
+// running statistics of a BatchNorm column: momentum step towards the batch mean and the UNBIASED batch variance
+__device__ __forceinline__ void bn_running_step(float& rm, float& rv, const float mu, const float var, const float nf, const float mom) {
+    const float unb = var * (nf / (nf - 1.0f));
+    rm += mom * (mu - rm);
+    rv += mom * (unb - rv);
+}
+// the step's loss and correct sums into the epoch's statistics (last wave: keeps the read-modify-write off wave 0)
+__device__ __forceinline__ void chain_step_stats(const ChainArgs& a, const ChainStep& cs, const float* red_l, const int Bp, const int tid,
+                                                 const int cgidx) {
+    if (tid == CHAIN_THREADS - 64 && a.stats) {
+        float ls = 0.f, ncor = 0.f;
+        for (int b = 0; b < Bp; ++b) { ls += red_l[b]; ncor += red_l[Bp + b]; }
+        DevStats& st = a.stats[(int64_t)cgidx * a.E + cs.epoch];
+        st.train_loss += (double)ls;
+        st.train_corr += (long long)ncor;
+        if (!(fabsf(ls) <= 3.0e38f)) atomicMax(&a.status[cgidx], 1);   // (never downgrades a timeout mark 2 set by a sweep unit of the same launch)
+    }
+}
+
 #ifdef MFAS_CHAIN_TIMING
 #define CT_STAMP(slot) do { if (threadIdx.x == 0 && bid == 0 && cs.gstep == 3) a.status[64 + (slot)] = (int32_t)(__builtin_readcyclecounter() - ct0); } while (0)
 // debug checksums (schedule bit-identity hunts): XOR of the bits of a tile wave's register image, candidate 0, global step 0
@@ -599,9 +621,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const ChainStep& 
                     rstd_l[i * Rp + r] = rstd;
                     if (colok) {   // running stats: momentum 0.1, unbiased variance
                         float rm = vecW[vbl + VEC_RM * Rp + r], rv = vecW[vbl + VEC_RV * Rp + r];
-                        const float unb = var * (nf / (nf - 1.0f));
-                        rm += g.bn_mom * (mu - rm);
-                        rv += g.bn_mom * (unb - rv);
+                        bn_running_step(rm, rv, mu, var, nf, g.bn_mom);
                         W[vb + VEC_RM * Rp + r] = rm;
                         W[vb + VEC_RV * Rp + r] = rv;
                     }
@@ -689,14 +709,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const ChainStep& 
         softmax_rows<MB>(a, cs, lg_l, SC, red_l, lab_l, nvalid, nf, tid, cand_order(a.order, g, cgidx));
     }
     lds_barrier();
-    if (tid == CHAIN_THREADS - 64 && a.stats) {   // last wave: keeps the read-modify-write of the statistics off wave 0
-        float ls = 0.f, ncor = 0.f;
-        for (int b = 0; b < Bp; ++b) { ls += red_l[b]; ncor += red_l[Bp + b]; }
-        DevStats& st = a.stats[(int64_t)cgidx * a.E + cs.epoch];
-        st.train_loss += (double)ls;
-        st.train_corr += (long long)ncor;
-        if (!(fabsf(ls) <= 3.0e38f)) atomicMax(&a.status[cgidx], 1);   // (never downgrades a timeout mark 2 set by a sweep unit of the same launch)
-    }
+    chain_step_stats(a, cs, red_l, Bp, tid, cgidx);
     CT_STAMP(7);
     // dlogits -> global (dy operand of the HEAD segment); head-bias Adam
     {
@@ -1857,9 +1870,9 @@ __device__ __forceinline__ void lean_res_store(const ChainArgs& a, const int bid
 //     so two workgroups of the launch (its dynamic LDS size is also the sweep units') still share a CU;
 //   * per-cell "dy is out" flags become arrival COUNTERS (every part adds 1 behind its exchange poll — whose returned load implies
 //     the wave's earlier stores were acknowledged — so no extra drain; target = NS * (step + 1)).
-// The arithmetic per row block is chain_body's (same products in the same even / odd MFMA chains, same reductions): every schedule
-// stays bit-identical (tests/test_gpu_parity.py::test_same_group_launch_fuzz_bit_identical, ::test_full_size_properties,
-// ::test_chain_split_bit_identical).
+// The arithmetic per row block is chain_body's (same products in the same even / odd MFMA chains, same reductions; bn_running_step and
+// chain_step_stats are the same functions, the rest is transcribed statement by statement): every schedule stays bit-identical
+// (tests/test_gpu_parity.py::test_same_group_launch_fuzz_bit_identical, ::test_full_size_properties, ::test_chain_split_bit_identical).
 // ------------------------------------------------------------------------------------------------
 #define XCH_SLOTS 7
 #define XCH_SENT 0xFFFFFFFFu
@@ -2155,9 +2168,7 @@ __device__ __forceinline__ void chain_split(const ChainArgs& a, const ChainStep&
                     rstd_l[i * NCOL + vcol] = rstd;
                     if (colok) {
                         float rm = vc[VEC_RM * NCOL + vcol], rv = vc[VEC_RV * NCOL + vcol];
-                        const float unb = var * (nf / (nf - 1.0f));
-                        rm += g.bn_mom * (mu - rm);
-                        rv += g.bn_mom * (unb - rv);
+                        bn_running_step(rm, rv, mu, var, nf, g.bn_mom);
                         W[vb + VEC_RM * Rp + r] = rm;
                         W[vb + VEC_RV * Rp + r] = rv;
                     }
@@ -2243,14 +2254,7 @@ __device__ __forceinline__ void chain_split(const ChainArgs& a, const ChainStep&
     CS_STAMP(21);
     lds_barrier();
     if (part == 0) {
-        if (tid == CHAIN_THREADS - 64 && a.stats) {
-            float ls = 0.f, ncor = 0.f;
-            for (int b = 0; b < Bp; ++b) { ls += red_l[b]; ncor += red_l[Bp + b]; }
-            DevStats& st = a.stats[(int64_t)cgidx * a.E + cs.epoch];
-            st.train_loss += (double)ls;
-            st.train_corr += (long long)ncor;
-            if (!(fabsf(ls) <= 3.0e38f)) atomicMax(&a.status[cgidx], 1);
-        }
+        chain_step_stats(a, cs, red_l, Bp, tid, cgidx);
         float* dlg = sb + g.sb_dlog;
         for (int e = tid; e < Bp * Cp; e += CHAIN_THREADS) {
             const int b = e / Cp, c = e - b * Cp;
