@@ -125,6 +125,23 @@ def eval_me(hp):
     return 16
 
 
+def eval_build(hp, dtype):
+    """The k_eval build the dev pass runs for this geometry and table dtype with no switch set, as (MBE, NRBW, split, 16-bit rows,
+    B3): plan_layout's row blocks per wave (1, 2, 4, 8: three take the build for four, five to seven the one for eight) and
+    launch_eval's order of choice (m-blocks split over the waves at one or two row blocks, 16-bit rows there over bf16 tables; the
+    bf16 x 3 build at two row blocks per wave over bf16 tables; else the plain build)."""
+    nrb = -(-hp.R // 16)
+    nrbw = (nrb + 3) // 4
+    nrbw = 4 if nrbw == 3 else (8 if 4 < nrbw < 8 else nrbw)
+    mbe = eval_me(hp) // 16
+    bf16 = dtype == "bfloat16"
+    if nrbw == 1 and nrb <= 2:
+        return (mbe, 1, nrb, bf16, False)
+    if bf16 and nrbw == 2:
+        return (mbe, 2, 0, True, True)
+    return (mbe, nrbw, 0, False, False)
+
+
 # ------------------------------------------------------------------------------------------------ GPU plumbing
 def _torch():
     import torch
@@ -221,6 +238,9 @@ def test_entry_points_vs_ref64(dev, case, dtype):
                     _, _, lo, hi = R64.dev_stats(lg, Ml, hp, TAU_LOGITS, labels=t["label"][row0:row0 + nrows],
                                                  vlogit=f.get("vlogit"), slogit=f.get("slogit"))
                     assert lo <= corr <= hi, f"{tag} forward count rows {row0}+{nrows} {env}: {corr} not in [{lo}, {hi}]"
+                else:       # the multi-label head counts F1-samples in 32.32 fixed point
+                    _, _, lo, hi = R64.dev_stats(lg, Ml, hp, TAU_LOGITS, z=t["multilabel"][row0:row0 + nrows], pos_weight=pos_weight(hp))
+                    assert lo <= corr <= hi, f"{tag} forward F1 sum rows {row0}+{nrows} {env}: {corr} not in [{lo}, {hi}]"
         if env:
             ep.close()
     # 2. forward_train (+ running statistics) and backward of an arbitrary dL/dlogits
