@@ -201,6 +201,72 @@ def dev():
             print(f"  {k:40s} {R64.RATIOS[k]:.4g}")
 
 
+# ------------------------------------------------------------------------------------------------ shared blocks
+def eval_envs(hp):
+    """The dev-pass builds the switches select at this R: the default one, and where the geometry has them the MFAS_EVAL_NO_* ones."""
+    envs = [{}]
+    if hp.R <= 32 or 65 <= hp.R <= 128:
+        envs += [{"MFAS_EVAL_NO_MSPLIT": "1"}, {"MFAS_EVAL_NO_X16": "1"}, {"MFAS_EVAL_NO_B3": "1"}, {"MFAS_EVAL_NO_WL": "1"}]
+    return envs
+
+
+def check_eval_forward(ep, hp, conf, p0, t, tab, tag, rec, env=None, k=0):
+    """forward (eval) of candidate k over the ragged row ranges {1, ME - 1, ME + 1, N_EVAL - row0} at row0 = 0 and 5: the logits
+    elementwise against ref64, the count (rows, or the 32.32 fixed-point F1 sum) inside [lo, hi]."""
+    ME = eval_me(hp)
+    for row0 in (0, 5):
+        for nrows in sorted({1, ME - 1, ME + 1, N_EVAL - row0}):
+            got, corr = ep.forward(k, tab, row0=row0, nrows=nrows, count=True)
+            f = feats_of(t, row0, nrows)
+            lg, Ml, _ = R64.forward(p0, conf, hp, f, False)
+            R64.assert_close64(got.cpu().numpy(), lg, Ml, TAU_LOGITS, f"{tag} forward rows {row0}+{nrows} {env or ''}",
+                               record=f"forward/{rec}")
+            if hp.loss_mode == 0:
+                _, _, lo, hi = R64.dev_stats(lg, Ml, hp, TAU_LOGITS, labels=t["label"][row0:row0 + nrows],
+                                             vlogit=f.get("vlogit"), slogit=f.get("slogit"))
+                assert lo <= corr <= hi, f"{tag} forward count rows {row0}+{nrows} {env}: {corr} not in [{lo}, {hi}]"
+            else:       # the multi-label head counts F1-samples in 32.32 fixed point
+                _, _, lo, hi = R64.dev_stats(lg, Ml, hp, TAU_LOGITS, z=t["multilabel"][row0:row0 + nrows], pos_weight=pos_weight(hp))
+                assert lo <= corr <= hi, f"{tag} forward F1 sum rows {row0}+{nrows} {env}: {corr} not in [{lo}, {hi}]"
+
+
+def check_train_passes(pop, dev, hp, conf, p0, t, tab, seed, tag, rec, k=0, drop_seed=None, tau_runstat=None):
+    """forward_train of the first B rows (+ the running statistics it leaves) and backward of an arbitrary dL/dlogits, candidate k
+    against ref64.  Returns ref64's cache of that forward."""
+    torch = _torch()
+    nb = hp.B
+    step = 3
+    f = feats_of(t, 0, nb)
+    got = pop.forward_train(k, tab, 0, nb, step=step).cpu().numpy()
+    lg, Ml, cache = R64.forward(p0, conf, hp, f, True, seed=seed if drop_seed is None else drop_seed, step=step)
+    R64.assert_close64(got, lg, Ml, TAU_LOGITS, f"{tag} forward_train", record=f"forward_train/{rec}")
+    if hp.bn:
+        rs, Mrs = R64.running_stats(p0, hp, cache)
+        sd = state_np(pop, k)
+        for key in rs:
+            R64.assert_close64(sd[key], rs[key], Mrs[key], TAU_RUNSTAT if tau_runstat is None else tau_runstat,
+                               f"{tag} forward_train {key}", record=f"running_stats/{rec}")
+    pop.set_state_dict(k, p0)
+    rng = np.random.default_rng(seed)
+    dl = (rng.standard_normal((nb, hp.C)) / nb).astype(F32)
+    dl[rng.random((nb, hp.C)) < 0.1] *= F32(1e-3)         # a spread of gradient sizes: small tiles are held to their own scale
+    from mfas_amd.engine import flat_layout
+    flat = pop.backward(k, tab, torch.from_numpy(dl).to(dev), 0, nb, step=step).cpu().numpy()
+    G, MG = R64.backward(p0, hp, cache, dl)
+    layout, _ = flat_layout(conf, hp)
+    for key, shape, off in layout:
+        if key in G:
+            R64.assert_close64(flat[off:off + int(np.prod(shape))].reshape(shape), G[key], MG[key], TAU_GRAD, f"{tag} backward {key}",
+                               record=f"backward/{rec}")
+    return cache
+
+
+def dev_epoch_rows(B):
+    """Rows of the train table of the one-epoch call: two full batches and a ragged one of at least two rows."""
+    ntr = 2 * B + max(1, B // 2)
+    return ntr + 1 if ntr % B == 1 else ntr
+
+
 # ------------------------------------------------------------------------------------------------ the tests
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -208,7 +274,6 @@ def dev():
 def test_entry_points_vs_ref64(dev, case, dtype):
     """forward (eval) over ragged row ranges, forward_train + running statistics, backward of arbitrary dlogits, and one epoch of
     train() with a dev table, against ref64; then (f32, single-label) three train steps against the float32 oracle."""
-    torch = _torch()
     cid = case[0]
     hp = case_hyper(case)
     seed = 1000 + CASE_IDS.index(cid)
@@ -217,61 +282,20 @@ def test_entry_points_vs_ref64(dev, case, dtype):
     tab = gpu_table(t, dtype, dev)
     pop = make_pop(hp, conf, dev, seed)
     pop.set_state_dict(0, p0)
-    ME = eval_me(hp)
     tag = f"{cid} R{hp.R} C{hp.C} B{hp.B} {dtype}"
     # 1. eval forward: every row range, every dev-pass build the switches select
-    envs = [{}]
-    if hp.R <= 32 or 65 <= hp.R <= 128:
-        envs += [{"MFAS_EVAL_NO_MSPLIT": "1"}, {"MFAS_EVAL_NO_X16": "1"}, {"MFAS_EVAL_NO_B3": "1"}, {"MFAS_EVAL_NO_WL": "1"}]
-    for env in envs:
+    for env in eval_envs(hp):
         ep = pop if not env else make_pop(hp, conf, dev, seed, env=env)
         if env:
             ep.set_state_dict(0, p0)
-        for row0 in (0, 5):
-            for nrows in sorted({1, ME - 1, ME + 1, N_EVAL - row0}):
-                got, corr = ep.forward(0, tab, row0=row0, nrows=nrows, count=True)
-                f = feats_of(t, row0, nrows)
-                lg, Ml, _ = R64.forward(p0, conf, hp, f, False)
-                R64.assert_close64(got.cpu().numpy(), lg, Ml, TAU_LOGITS, f"{tag} forward rows {row0}+{nrows} {env or ''}",
-                                   record=f"forward/{dtype}")
-                if hp.loss_mode == 0:
-                    _, _, lo, hi = R64.dev_stats(lg, Ml, hp, TAU_LOGITS, labels=t["label"][row0:row0 + nrows],
-                                                 vlogit=f.get("vlogit"), slogit=f.get("slogit"))
-                    assert lo <= corr <= hi, f"{tag} forward count rows {row0}+{nrows} {env}: {corr} not in [{lo}, {hi}]"
-                else:       # the multi-label head counts F1-samples in 32.32 fixed point
-                    _, _, lo, hi = R64.dev_stats(lg, Ml, hp, TAU_LOGITS, z=t["multilabel"][row0:row0 + nrows], pos_weight=pos_weight(hp))
-                    assert lo <= corr <= hi, f"{tag} forward F1 sum rows {row0}+{nrows} {env}: {corr} not in [{lo}, {hi}]"
+        check_eval_forward(ep, hp, conf, p0, t, tab, tag, dtype, env)
         if env:
             ep.close()
     # 2. forward_train (+ running statistics) and backward of an arbitrary dL/dlogits
-    nb = hp.B
-    step = 3
-    f = feats_of(t, 0, nb)
-    got = pop.forward_train(0, tab, 0, nb, step=step).cpu().numpy()
-    lg, Ml, cache = R64.forward(p0, conf, hp, f, True, seed=seed, step=step)
-    R64.assert_close64(got, lg, Ml, TAU_LOGITS, f"{tag} forward_train", record=f"forward_train/{dtype}")
-    if hp.bn:
-        rs, Mrs = R64.running_stats(p0, hp, cache)
-        sd = state_np(pop)
-        for key in rs:
-            R64.assert_close64(sd[key], rs[key], Mrs[key], TAU_RUNSTAT, f"{tag} forward_train {key}", record=f"running_stats/{dtype}")
-    pop.set_state_dict(0, p0)
-    rng = np.random.default_rng(seed)
-    dl = (rng.standard_normal((nb, hp.C)) / nb).astype(F32)
-    dl[rng.random((nb, hp.C)) < 0.1] *= F32(1e-3)         # a spread of gradient sizes: small tiles are held to their own scale
-    from mfas_amd.engine import flat_layout
-    flat = pop.backward(0, tab, torch.from_numpy(dl).to(dev), 0, nb, step=step).cpu().numpy()
-    G, MG = R64.backward(p0, hp, cache, dl)
-    layout, _ = flat_layout(conf, hp)
-    for key, shape, off in layout:
-        if key in G:
-            R64.assert_close64(flat[off:off + int(np.prod(shape))].reshape(shape), G[key], MG[key], TAU_GRAD, f"{tag} backward {key}",
-                               record=f"backward/{dtype}")
+    check_train_passes(pop, dev, hp, conf, p0, t, tab, seed, tag, dtype)
     # 3. one epoch of train() with a dev table: the dev statistics on the engine's parameters after the call
     pop.set_state_dict(0, p0)
-    ntr = 2 * hp.B + max(1, hp.B // 2)
-    if ntr % hp.B == 1:
-        ntr += 1
+    ntr = dev_epoch_rows(hp.B)
     ttr = case_table(case, hp, ntr, seed + 1, dtype)
     etas = O.eta_sequence(1e-3, 1e-6, 1, 2, ntr / hp.B, -(-ntr // hp.B))
     stats, status = pop.train(gpu_table(ttr, dtype, dev), tab, 1, etas)

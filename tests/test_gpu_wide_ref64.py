@@ -166,14 +166,25 @@ def setup(case, dev, order_mode="shared"):
     return hp, ehp, seed, confs, p0s, seeds, pop
 
 
-def run_train_steps(dev, case, order_mode, full, steps, rec=None):
-    """train(max_steps = j) of the case's K = 3 candidates, `steps` against ref64 (test_gpu_train_ref64's check) under the case's taus."""
+def edit_inputs(edit, hp, confs, p0s, t, dtype):
+    """Every candidate's parameters and the shared table passed through edit(conf, hp, p0, t, dtype) -> (p0, t) (the table as
+    candidate 0's call returns it); edit None: unchanged."""
+    if edit is None:
+        return p0s, t
+    out = [edit(confs[k], hp, p0s[k], t, dtype) for k in range(len(confs))]
+    return [p for p, _ in out], out[0][1]
+
+
+def run_train_steps(dev, case, order_mode, full, steps, rec=None, edit=None):
+    """train(max_steps = j) of the case's K = 3 candidates, `steps` against ref64 (test_gpu_train_ref64's check) under the case's taus.
+    edit: the inputs changed before the engine and ref64 see them (tests/test_gpu_inputs_ref64.py)."""
     torch = G._torch()
     cid, dtype = case[0], case[9]
     hp, ehp, seed, confs, p0s, seeds, pop = setup(case, dev, order_mode)
     try:
         assert pop.schedule()["wide"] == 1
         N, t, order, etas = train_inputs(case, hp, ehp, seed, full)
+        p0s, t = edit_inputs(edit, hp, confs, p0s, t, dtype)
         S, ST = GT.engine_states(pop, G.gpu_table(t, dtype, dev), p0s, etas, torch.from_numpy(order).to(dev), steps)
     finally:
         pop.close()

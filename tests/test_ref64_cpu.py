@@ -70,12 +70,17 @@ def test_bce_and_f1_match_the_oracle():
 
 
 # ------------------------------------------------------------------------------------------------ calibration on the GPU shapes
-def oracle_case(case, dtype):
-    """The float32 oracle and ref64 on exactly the inputs test_gpu_ref64 gives the engine: worst ratio per quantity."""
+def oracle_case(case, dtype, seed=None, edit=None):
+    """The float32 oracle and ref64 on exactly the inputs test_gpu_ref64 gives the engine: worst ratio per quantity.
+    edit(conf, hp, p0, t, dtype) -> (p0, t): the parameters and the table changed before either side sees them
+    (tests/test_inputs_cpu.py)."""
     hp = G.case_hyper(case)
-    seed = 1000 + G.CASE_IDS.index(case[0]) if case[0] in G.CASE_IDS else 7
+    if seed is None:
+        seed = 1000 + G.CASE_IDS.index(case[0]) if case[0] in G.CASE_IDS else 7
     conf, p0 = G.case_params(case, hp, seed)
     t = G.case_table(case, hp, G.N_EVAL, seed, dtype)
+    if edit is not None:
+        p0, t = edit(conf, hp, p0, t, dtype)
     out = {}
     f = G.feats_of(t)
     lg32, _ = O.forward({k: v.copy() for k, v in p0.items()}, conf, hp, f, False)
@@ -363,14 +368,16 @@ def oracle_steps(conf, hp, p0, t, order, etas, seed, steps, taus, tag, mut="", w
     return worst
 
 
-def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False, N=None, steps=(1, 2, 3)):
+def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False, N=None, steps=(1, 2, 3), edit=None):
     """Steps of train() as test_gpu_train_ref64 sets them up (N rows: by default one full batch and the ragged one), the float32
-    oracle checked step by step on `steps`: worst ratio per quantity."""
+    oracle checked step by step on `steps`: worst ratio per quantity.  edit: as in oracle_case."""
     hp = G.case_hyper(case)
     seed = GT.SEED0 + G.CASE_IDS.index(case[0]) if seed is None else seed
     conf, p0 = G.case_params(case, hp, seed)
     N = GT.train_rows(hp.B) if N is None else N
     t = G.case_table(case, hp, N, seed, dtype)
+    if edit is not None:
+        p0, t = edit(conf, hp, p0, t, dtype)
     order = GT.make_order(N, seed)
     wrong = GT.make_order(N, seed, 2)[1]            # another candidate's order
     return oracle_steps(conf, hp, p0, t, order, GT.step_etas(N, hp.B), seed, tuple(steps), GT.TAUS, case[0], mut, wrong)

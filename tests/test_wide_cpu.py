@@ -21,15 +21,19 @@ F32 = np.float32
 
 
 # ------------------------------------------------------------------------------------------------ calibration
-def wide_oracle_case(case, k, cells):
+def wide_oracle_case(case, k, cells, edit=None):
     """The float32 oracle and ref64 on the inputs test_gpu_wide_ref64 gives the engine for candidate k: worst ratio per quantity
-    (test_ref64_cpu.py::oracle_case for a batch that may be larger than the 83-row dev table)."""
+    (test_ref64_cpu.py::oracle_case for a batch that may be larger than the 83-row dev table; edit as there)."""
     bc, dtype = GW.base_case(case, cells), case[9]
     hp = G.case_hyper(bc)
     seed = GW.SEED0 + GW.WIDE_IDS.index(case[0])
     conf, p0 = G.case_params(bc, hp, seed + 10 * k)
     t = G.case_table(bc, hp, G.N_EVAL, seed, dtype)
     tb = t if hp.B <= G.N_EVAL else G.case_table(bc, hp, hp.B, seed + 5, dtype)
+    if edit is not None:
+        p_in = p0
+        p0, t = edit(conf, hp, p_in, t, dtype)
+        tb = t if hp.B <= G.N_EVAL else edit(conf, hp, p_in, tb, dtype)[1]
     out = {}
     f = G.feats_of(t)
     lg, Ml, _ = R64.forward(p0, conf, hp, f, False)
