@@ -151,7 +151,7 @@ __device__ __forceinline__ void gather_body(const GatherArgs& ga, const CandDev&
                                             const int32_t* order, const int tid) {
     const int eb = tab.dtype == MFAS_DT_F32 ? 4 : 2;
     const int32_t* ordp = cand_order(order, g, cd.gidx);
-    uint32_t used = 0;            // bit kind * 4 + tap
+    uint32_t used = 0;            // bit kind * MFAS_MAX_TAPS + tap
     for (int i = 0; i < cd.L; ++i) used |= (1u << cd.conf[i][0]) | (1u << (MFAS_MAX_TAPS + cd.conf[i][1]));
 #pragma unroll
     for (int s = 0; s < 2; ++s) {

@@ -92,9 +92,9 @@ def batch_of(t, order_k, B, j):
     return {k: v[idx] for k, v in t.items()}, ep
 
 
-def step_etas(N, B):
+def step_etas(N, B, eta_max=1e-3, eta_min=1e-6):
     nb = -(-N // B)
-    return O.eta_sequence(1e-3, 1e-6, 1, 2, N / B, EPOCHS * nb)
+    return O.eta_sequence(eta_max, eta_min, 1, 2, N / B, EPOCHS * nb)
 
 
 def train_rows(B, full=1):
@@ -189,29 +189,36 @@ TRAIN_SCHEDULES.update({
 SCHED_CONFS = ([[3, 3, 0], [1, 2, 1]], [[0, 3, 2]], [[2, 1, 0], [3, 0, 1], [1, 1, 0]], [[1, 0, 1]])
 
 
-def schedule_inputs(name, order_mode, full=1):
+def schedule_inputs(name, order_mode, full=1, entry=None, hyper=None, widths=W_A, sched_confs=SCHED_CONFS):
     """What a TRAIN_SCHEDULES entry trains, as numpy (no device): hyper-parameters, K >= 3 candidates of different depth and
     nonlinearity with their own dropout seeds and initial parameters, a bf16 train table of `full` full batches and a ragged one,
-    a shared or a per-candidate sample order, the learning rates."""
+    a shared or a per-candidate sample order, the learning rates.
+    entry: a tuple like TRAIN_SCHEDULES' for a name that table does not hold; hyper(hp) -> hp: the hyper-parameters changed (its
+    eta_max / eta_min give the learning rates); widths, sched_confs: other tap widths and the configurations that select them
+    (tests/test_axes_cpu.py).  The defaults are what every other file trains."""
     from tests.helpers import engine_hyper
-    R, C, B, env, cc, K, tap_bits, check = TRAIN_SCHEDULES[name]
-    hp = O.Hyper(R=R, C=C, B=B, bn=True, drpt=0.5, s_sizes=W_A["s"], v_sizes=W_A["v"], epochs=EPOCHS)
-    confs = [np.array(SCHED_CONFS[k % len(SCHED_CONFS)]) for k in range(K)]
+    R, C, B, env, cc, K, tap_bits, check = entry or TRAIN_SCHEDULES[name]
+    hp = O.Hyper(R=R, C=C, B=B, bn=True, drpt=0.5, s_sizes=widths["s"], v_sizes=widths["v"], epochs=EPOCHS)
+    if hyper is not None:
+        hp = hyper(hp)
+    confs = [np.array(sched_confs[k % len(sched_confs)]) for k in range(K)]
     seeds = [5 + 3 * k for k in range(K)]
     ehp = engine_hyper(hp)
     ehp.tap_bits = tap_bits
     ehp.order_per_candidate = order_mode == "per_candidate"
     p0s = [O.init_params(c, hp, 40 + k, perturb_bn=True) for k, c in enumerate(confs)]
     N = train_rows(B, full)
-    t = case_table((name, R, C, B, W_A, None, True, 0.5, ""), hp, N, 61, "bfloat16")
+    t = case_table((name, R, C, B, widths, None, hp.bn, hp.drpt, ""), hp, N, 61, "bfloat16")
     order = make_order(N, 7, K if ehp.order_per_candidate else None)
-    return dict(hp=hp, ehp=ehp, confs=confs, seeds=seeds, p0s=p0s, N=N, t=t, dtype="bfloat16", order=order, etas=step_etas(N, B))
+    return dict(hp=hp, ehp=ehp, confs=confs, seeds=seeds, p0s=p0s, N=N, t=t, dtype="bfloat16", order=order,
+                etas=step_etas(N, B, hp.eta_max, hp.eta_min))
 
 
-def schedule_pop(name, inp, dev):
-    """The population of a TRAIN_SCHEDULES entry under the entry's switches, its schedule asserted with pop.schedule()."""
+def schedule_pop(name, inp, dev, entry=None):
+    """The population of a TRAIN_SCHEDULES entry (or of `entry`, a tuple like the table's) under the entry's switches, its schedule
+    asserted with pop.schedule()."""
     from mfas_amd import Population
-    R, C, B, env, cc, K, tap_bits, check = TRAIN_SCHEDULES[name]
+    R, C, B, env, cc, K, tap_bits, check = entry or TRAIN_SCHEDULES[name]
     os.environ.update(env)
     try:
         pop = Population(inp["ehp"], inp["confs"], dev, drop_seeds=inp["seeds"], chunk_cols=cc)
