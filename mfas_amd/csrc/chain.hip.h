@@ -356,9 +356,19 @@ __device__ __forceinline__ void softmax_rows_lean(const ChainArgs& a, float* lg_
     }
 }
 
-// Two pieces of the general chain's arithmetic that chain_body and chain_split both call (one statement each; the rest of the column
-// arithmetic is transcribed in both and pinned by the parity tests — as shared functions it changed the generated code of every general-
-// chain kernel, profiles/chain_shared_arith_codeobj.log):
+// The arithmetic the forms of the train-step chain state ONCE (profiles/chain_shared_loss_adam.log: code objects, bytes A/B, timings):
+//   bn_running_step, loss_rows                          chain_body, chain_split
+//   chain_step_stats, column_vec_adam, head_bias_adam   chain_body, chain_split, k_chain_wide (wide.hip.h)
+//   alpha_adam                                          chain_body, k_chain_wide (chain_split takes no alphas)
+// Still transcribed, pinned by the parity and ref64 tests:
+//   the forward / backward column of a cell: as shared functions they cost the 128-VGPR builds registers and scratch
+//     (profiles/chain_shared_arith_codeobj.log);
+//   the sums of the sweep's partial slabs: one function for the three forms made chain_split's step ~0.5 us (1.5 %) slower at one
+//     candidate, outside the parent library's own run-to-run range;
+//   the row losses of the wide kernel (wide_softmax_rows = softmax_rows_nc at 16 lanes x 16 classes, wide_bce_rows = bce_rows at
+//     16 lanes): one core per pair changed the generated code of the lean-chain kernels, which call softmax_rows / bce_rows too;
+//   chain_lean_tail's rolled statistics, head-bias and alpha blocks.
+
 // running statistics of a BatchNorm column: momentum step towards the batch mean and the UNBIASED batch variance
 __device__ __forceinline__ void bn_running_step(float& rm, float& rv, const float mu, const float var, const float nf, const float mom) {
     const float unb = var * (nf / (nf - 1.0f));
@@ -375,6 +385,52 @@ __device__ __forceinline__ void chain_step_stats(const ChainArgs& a, const Chain
         st.train_loss += (double)ls;
         st.train_corr += (long long)ncor;
         if (!(fabsf(ls) <= 3.0e38f)) atomicMax(&a.status[cgidx], 1);   // (never downgrades a timeout mark 2 set by a sweep unit of the same launch)
+    }
+}
+// Adam on a column's vector parameters, by the column's owner lane: the bias (gradient db), under BatchNorm gamma and beta as well;
+// pw / pm / pv = the parameters and moments the caller read ahead, ob / og / obe = where they live in the W, m and v planes
+__device__ __forceinline__ void column_vec_adam(float* W, float* Mv, float* Vv, const int64_t ob, const int64_t og, const int64_t obe,
+                                                float (&pw)[3], float (&pm)[3], float (&pv)[3], const float db, const float dgam,
+                                                const float dbet, const bool bn, const AdamC& ac) {
+    adam1(pw[0], pm[0], pv[0], db, ac);
+    W[ob] = pw[0]; Mv[ob] = pm[0]; Vv[ob] = pv[0];
+    if (bn) {
+        adam1(pw[1], pm[1], pv[1], dgam, ac);
+        W[og] = pw[1]; Mv[og] = pm[1]; Vv[og] = pv[1];
+        adam1(pw[2], pm[2], pv[2], dbet, ac);
+        W[obe] = pw[2]; Mv[obe] = pm[2]; Vv[obe] = pv[2];
+    }
+}
+// Adam on a cell's alpha (plane offset o): d(alpha) = sigma'(alpha) * tot, tot = sum_{b,r} dy[b,r] * (yS_raw - yV_raw)[b,r]
+__device__ __forceinline__ void alpha_adam(float* W, float* Mv, float* Vv, const int64_t o, float w, float m, float v, const float tot,
+                                           const AdamC& ac) {
+    const float sg = 1.0f / (1.0f + expf(-w));
+    adam1(w, m, v, tot * sg * (1.0f - sg), ac);
+    W[o] = w; Mv[o] = m; Vv[o] = v;
+}
+// Adam on the head bias of one class (plane offset o; w, m, v as the caller holds them): the gradient is the column sum of dlogits in
+// batch order — dl = the class's element of row 0, rows `stride` floats apart
+__device__ __forceinline__ void head_bias_adam(float* W, float* Mv, float* Vv, const int64_t o, float w, float m, float v, const float* dl,
+                                               const int stride, const int Bp, const AdamC& ac) {
+    float gsum = 0.f;
+    for (int b = 0; b < Bp; ++b) gsum += dl[b * stride];
+    adam1(w, m, v, gsum, ac);
+    W[o] = w; Mv[o] = m; Vv[o] = v;
+}
+// the loss of the LDS logits, by the head: weighted BCE (loss_mode 1), the eight-lanes-per-row softmax (<= 64 classes, single task —
+// every NTU / AV-MNIST head: ~1/3 of the instructions on the serial path) or the general softmax, each on the threads it needs
+template <int MB>
+__device__ __forceinline__ void loss_rows(const ChainArgs& a, const ChainStep& cs, float* lg_l, const int SC, float* red_l, const int* lab_l,
+                                          const int nvalid, const float nf, const int tid, const int cgidx) {
+    constexpr int Bp = MB * 16;
+    constexpr int LPR = (STEP_THREADS / Bp) < 16 ? (STEP_THREADS / Bp) : 16;
+    const Geo& g = a.g;
+    if (g.loss_mode == 1) {
+        if (tid < 4 * Bp) bce_rows(lg_l, SC, red_l, Bp, lab_l, a.tab.multilabel, a.pos_w, g.C, g.Cp, nvalid, tid);
+    } else if (g.Cp <= 64 && !g.multitask) {
+        if (tid < 8 * Bp) softmax_rows_lean<MB>(a, lg_l, SC, red_l, lab_l, nvalid, nf, tid);
+    } else if (tid < LPR * Bp) {
+        softmax_rows<MB>(a, cs, lg_l, SC, red_l, lab_l, nvalid, nf, tid, cand_order(a.order, g, cgidx));
     }
 }
 
@@ -401,7 +457,6 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const ChainStep& 
     // (co-scheduled builds of the two-batch-block chain live in 128 VGPRs: 4 tiles per batch in the same-group launch, where the chain
     //  is on the critical path, 2 under the other group's sweep — k_step<2,*,4,false> spilled 31 registers with 8, none with 2)
     constexpr int CHAIN_TW = (MB >= 2 && !PF) ? (COH ? 4 : 2) : (MB >= 4 ? 4 : 8);
-    constexpr int LPR = (STEP_THREADS / Bp) < 16 ? (STEP_THREADS / Bp) : 16;   // softmax lanes per batch row
     const int Rp = g.Rp, nrb = g.nrb, Cp = g.Cp, ncb = g.ncb, R = g.R, C = g.C, L = cd.L;
     const int SX = Rp + 4, SC = Cp + 4;
     // LDS kept close to the sweep's so both bodies can share one launch: ping-pong activation buffers (out_i
@@ -698,15 +753,8 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const ChainStep& 
             const int b = e / Cp, c = e - b * Cp;
             lg_l[b * SC + c] = (b < nvalid && c < C) ? a.dlogits_in[(int64_t)b * C + c] : 0.f;
         }
-    } else if (g.loss_mode == 1) {
-        if (tid < 4 * Bp) bce_rows(lg_l, SC, red_l, Bp, lab_l, a.tab.multilabel, a.pos_w, C, Cp, nvalid, tid);
-    } else if (Cp <= 64 && !g.multitask) {
-        // (round 6: <= 64 classes, single task — every NTU / AV-MNIST head — take the eight-lanes-per-row form written for the lean chain:
-        //  ~1/3 of the instructions on the serial path; chain_body and chain_split call the same function, so every schedule of the
-        //  general chain still rounds identically)
-        if (tid < 8 * Bp) softmax_rows_lean<MB>(a, lg_l, SC, red_l, lab_l, nvalid, nf, tid);
-    } else if (tid < LPR * Bp) {
-        softmax_rows<MB>(a, cs, lg_l, SC, red_l, lab_l, nvalid, nf, tid, cand_order(a.order, g, cgidx));
+    } else {
+        loss_rows<MB>(a, cs, lg_l, SC, red_l, lab_l, nvalid, nf, tid, cgidx);
     }
     lds_barrier();
     chain_step_stats(a, cs, red_l, Bp, tid, cgidx);
@@ -719,14 +767,9 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const ChainStep& 
             stc1<COH>(dlg + e, lg_l[b * SC + c]);
         }
         const int hc = tid - (CHAIN_THREADS - 256);   // head-bias columns on the upper four waves
-        if (hc >= 0 && hc < C) {
-            float gsum = 0.f;
-            for (int b = 0; b < Bp; ++b) gsum += lg_l[b * SC + hc];
-            const int64_t o = cvec_off + g.vec_head + hc;
-            float w = vecW[g.vec_head + hc], m = vecM[g.vec_head + hc], v = vecV[g.vec_head + hc];
-            adam1(w, m, v, gsum, ac);
-            W[o] = w; Mv[o] = m; Vv[o] = v;
-        }
+        if (hc >= 0 && hc < C)
+            head_bias_adam(W, Mv, Vv, cvec_off + g.vec_head + hc, vecW[g.vec_head + hc], vecM[g.vec_head + hc], vecV[g.vec_head + hc],
+                           lg_l + hc, SC, Bp, ac);
     }
     if (pf) {
 #pragma unroll
@@ -824,16 +867,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const ChainStep& 
                     stc1<COH>(dy_g + b * Rp + r, dy);
                 }
             const float db = colsum(sdy);
-            if (lg == 0 && colok) {   // Adam on the column's vector parameters (one owner lane per column)
-                adam1(pw[0], pm[0], pv[0], db, ac);
-                W[ob] = pw[0]; Mv[ob] = pm[0]; Vv[ob] = pv[0];
-                if (g.bn) {
-                    adam1(pw[1], pm[1], pv[1], dgam, ac);
-                    W[og] = pw[1]; Mv[og] = pm[1]; Vv[og] = pv[1];
-                    adam1(pw[2], pm[2], pv[2], dbet, ac);
-                    W[obe] = pw[2]; Mv[obe] = pm[2]; Vv[obe] = pv[2];
-                }
-            }
+            if (lg == 0 && colok) column_vec_adam(W, Mv, Vv, ob, og, obe, pw, pm, pv, db, dgam, dbet, g.bn, ac);   // (one owner lane per column)
         }
         if (pf && i >= 1) {
 #pragma unroll
@@ -847,11 +881,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const ChainStep& 
         if (g.alphas && tid == 0) {
             float tot = 0.f;
             for (int w = 0; w < CHAIN_NW; ++w) tot += red_l[2 * Bp + w];
-            const int64_t o = vb + 5 * Rp;
-            float w = vecW[vbl + 5 * Rp], m = vecM[vbl + 5 * Rp], v = vecV[vbl + 5 * Rp];
-            const float sg = 1.0f / (1.0f + expf(-w));
-            adam1(w, m, v, tot * sg * (1.0f - sg), ac);
-            W[o] = w; Mv[o] = m; Vv[o] = v;
+            alpha_adam(W, Mv, Vv, vb + 5 * Rp, vecW[vbl + 5 * Rp], vecM[vbl + 5 * Rp], vecV[vbl + 5 * Rp], tot, ac);
         }
         if (g.alphas) lds_barrier();
         if constexpr (COH) {
@@ -1870,8 +1900,9 @@ __device__ __forceinline__ void lean_res_store(const ChainArgs& a, const int bid
 //     so two workgroups of the launch (its dynamic LDS size is also the sweep units') still share a CU;
 //   * per-cell "dy is out" flags become arrival COUNTERS (every part adds 1 behind its exchange poll — whose returned load implies
 //     the wave's earlier stores were acknowledged — so no extra drain; target = NS * (step + 1)).
-// The arithmetic per row block is chain_body's (same products in the same even / odd MFMA chains, same reductions; bn_running_step and
-// chain_step_stats are the same functions, the rest is transcribed statement by statement): every schedule stays bit-identical
+// The arithmetic per row block is chain_body's (same products in the same even / odd MFMA chains, same reductions).  The same functions
+// in both: bn_running_step, loss_rows, chain_step_stats, head_bias_adam, column_vec_adam; transcribed statement by statement: the slab
+// sums and the forward and backward column of a cell (activation, BatchNorm, dropout and their gradients).  Every schedule stays bit-identical
 // (tests/test_gpu_parity.py::test_same_group_launch_fuzz_bit_identical, ::test_full_size_properties, ::test_chain_split_bit_identical).
 // ------------------------------------------------------------------------------------------------
 #define XCH_SLOTS 7
@@ -1916,7 +1947,6 @@ __device__ __forceinline__ void chain_split(const ChainArgs& a, const ChainStep&
     const int l15 = lane & 15, lg = lane >> 4;
     const int Rp = g.Rp, nrb = 8, Cp = g.Cp, ncb = g.ncb, R = g.R, C = g.C, L = cd.L;
     const int SX = Rp + 4, SC = Cp + 4;
-    constexpr int LPR = 16;
     float* xo_l = lds;                                   // [2][16][SX] out_i ping-pong; backward: dy_i
     float* dy_l = xo_l;
     float* lg_l = xo_l + 2 * Bp * SX;                    // [16][SC]
@@ -2244,13 +2274,7 @@ __device__ __forceinline__ void chain_split(const ChainArgs& a, const ChainStep&
     if (lab_b >= 0 && lab_b < Bp) lab_l[lab_b] = lab_r;
     lds_barrier();
     CS_STAMP(6);
-    if (g.loss_mode == 1) {
-        if (tid < 4 * Bp) bce_rows(lg_l, SC, red_l, Bp, lab_l, a.tab.multilabel, a.pos_w, C, Cp, nvalid, tid);
-    } else if (Cp <= 64 && !g.multitask) {
-        if (tid < 8 * Bp) softmax_rows_lean<MB>(a, lg_l, SC, red_l, lab_l, nvalid, nf, tid);
-    } else if (tid < LPR * Bp) {
-        softmax_rows<MB>(a, cs, lg_l, SC, red_l, lab_l, nvalid, nf, tid, cand_order(a.order, g, cgidx));
-    }
+    loss_rows<MB>(a, cs, lg_l, SC, red_l, lab_l, nvalid, nf, tid, cgidx);
     CS_STAMP(21);
     lds_barrier();
     if (part == 0) {
@@ -2262,12 +2286,8 @@ __device__ __forceinline__ void chain_split(const ChainArgs& a, const ChainStep&
         }
         const int hc = tid - (CHAIN_THREADS - 256);
         if (hc >= 0 && hc < C) {
-            float gsum = 0.f;
-            for (int b = 0; b < Bp; ++b) gsum += lg_l[b * SC + hc];
             const int64_t o = cvec_off + g.vec_head + hc;
-            float w = vl[nvec + hc], m = Mv[o], v = Vv[o];
-            adam1(w, m, v, gsum, ac);
-            W[o] = w; Mv[o] = m; Vv[o] = v;
+            head_bias_adam(W, Mv, Vv, o, vl[nvec + hc], Mv[o], Vv[o], lg_l + hc, SC, Bp, ac);
         }
     }
     CS_STAMP(7);
@@ -2351,16 +2371,7 @@ __device__ __forceinline__ void chain_split(const ChainArgs& a, const ChainStep&
                 stc1<true>(dy_g + b * Rp + r, d4[q]);
             }
             const float db = colsum(sdy);
-            if (lg == 0 && colok) {
-                adam1(pw[0], pm[0], pv[0], db, ac);
-                W[ob] = pw[0]; Mv[ob] = pm[0]; Vv[ob] = pv[0];
-                if (g.bn) {
-                    adam1(pw[1], pm[1], pv[1], dgam, ac);
-                    W[og] = pw[1]; Mv[og] = pm[1]; Vv[og] = pv[1];
-                    adam1(pw[2], pm[2], pv[2], dbet, ac);
-                    W[obe] = pw[2]; Mv[obe] = pm[2]; Vv[obe] = pv[2];
-                }
-            }
+            if (lg == 0 && colok) column_vec_adam(W, Mv, Vv, ob, og, obe, pw, pm, pv, db, dgam, dbet, g.bn, ac);
         }
         if (!main_w) {
             if (help_w) {

@@ -342,22 +342,10 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain_wide(const ChainArgs 
     }
     if (a.logits_out) return;
     __syncthreads();
-    if (tid == CHAIN_THREADS - 64 && a.stats) {
-        float ls = 0.f, ncor = 0.f;
-        for (int b = 0; b < Bp; ++b) { ls += red_l[b]; ncor += red_l[Bp + b]; }
-        DevStats& st = a.stats[(int64_t)cgidx * a.E + cs.epoch];
-        st.train_loss += (double)ls;
-        st.train_corr += (long long)ncor;
-        if (!(fabsf(ls) <= 3.0e38f)) atomicMax(&a.status[cgidx], 1);
-    }
-    if (tid < C) {            // head-bias Adam: the column sum of dlogits in batch order
-        float gsum = 0.f;
-        for (int b = 0; b < Bp; ++b) gsum += sb[g.sb_dlog + (int64_t)b * Cp + tid];
-        const int64_t o = cvec_off + g.vec_head + tid;
-        float w = vecW[g.vec_head + tid], m = vecM[g.vec_head + tid], v = vecV[g.vec_head + tid];
-        adam1(w, m, v, gsum, ac);
-        W[o] = w; Mv[o] = m; Vv[o] = v;
-    }
+    chain_step_stats(a, cs, red_l, Bp, tid, cgidx);
+    if (tid < C)              // head-bias Adam over the dlogits of the whole batch
+        head_bias_adam(W, Mv, Vv, cvec_off + g.vec_head + tid, vecW[g.vec_head + tid], vecM[g.vec_head + tid], vecV[g.vec_head + tid],
+                       sb + g.sb_dlog + tid, Cp, Bp, ac);
 
     // ------------------------------------------------------------------ backward chain
     for (int i = L - 1; i >= 0; --i) {
@@ -454,16 +442,7 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain_wide(const ChainArgs 
                     }
                 }
                 const float db = colsum(sdy);
-                if (lg == 0 && colok) {
-                    adam1(pw[0], pm[0], pv[0], db, ac);
-                    W[ob] = pw[0]; Mv[ob] = pm[0]; Vv[ob] = pv[0];
-                    if (g.bn) {
-                        adam1(pw[1], pm[1], pv[1], dgam, ac);
-                        W[og] = pw[1]; Mv[og] = pm[1]; Vv[og] = pv[1];
-                        adam1(pw[2], pm[2], pv[2], dbet, ac);
-                        W[obe] = pw[2]; Mv[obe] = pm[2]; Vv[obe] = pv[2];
-                    }
-                }
+                if (lg == 0 && colok) column_vec_adam(W, Mv, Vv, ob, og, obe, pw, pm, pv, db, dgam, dbet, g.bn, ac);
             }
         }
         if (g.alphas) {   // d(alpha_i) = sigma'(alpha) * sum_{b,r} dy[b,r] * (yS_raw - yV_raw)[b,r], waves summed in order
@@ -473,11 +452,7 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain_wide(const ChainArgs 
             if (tid == 0) {
                 float tot = 0.f;
                 for (int w = 0; w < CHAIN_NW; ++w) tot += red_l[2 * Bp + w];
-                const int64_t o = vb + 5 * Rp;
-                float w = vecW[vbl + 5 * Rp], m = vecM[vbl + 5 * Rp], v = vecV[vbl + 5 * Rp];
-                const float sg = 1.0f / (1.0f + expf(-w));
-                adam1(w, m, v, tot * sg * (1.0f - sg), ac);
-                W[o] = w; Mv[o] = m; Vv[o] = v;
+                alpha_adam(W, Mv, Vv, vb + 5 * Rp, vecW[vbl + 5 * Rp], vecM[vbl + 5 * Rp], vecV[vbl + 5 * Rp], tot, ac);
             }
         }
     }
