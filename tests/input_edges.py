@@ -16,6 +16,11 @@ dup        every row equals row 0                                              b
 onelabel   every label is C - 1                                                the last valid class next to the padded ones
 dead       per cell, fusion bias r = 0 mod 3 set to -DEAD_BIAS and              a ReLU column exactly 0 over the batch, a sigmoid
            r = 1 mod 3 to +DEAD_BIAS                                           column saturated at 0 / 1, a large LeakyReLU column
+deadrelu   per cell, fusion bias r = 0 mod 3 set to -DEAD_BIAS, nothing else   the dead half of 'dead' alone: a ReLU column exactly 0 over the
+                                                                               batch in the FIRST cell under BatchNorm (var 0, d_y gated off)
+bigmean    per cell, fusion bias r = 1 mod 3 set to +DEAD_BIAS, nothing else   the other half alone: a ReLU / LeakyReLU column of n values near 64
+                                                                               with a spread of about 1 (the float32 batch sum rounds at the
+                                                                               scale of 64 n; ref64 judges it with batch_sum_term), a sigmoid at 1
 bighead    classifier weight and bias x 200 (CE heads only)                    |logit| 100-160, a one-hot softmax, CE up to 300 a row
 mlrows     multi-label targets: row 0 empty, row 1 full, rows 2..4 one         a row whose F1 denominator is 0; head bias -6, so
            positive (class 0, C - 1, `top`); head bias -6 on every class       nothing is predicted anywhere
@@ -31,7 +36,7 @@ import numpy as np
 from oracle import np_oracle as O
 
 F32 = np.float32
-HOWS = ("scaled", "tiny", "sparse", "offset", "dup", "onelabel", "dead", "bighead", "mlrows")
+HOWS = ("scaled", "tiny", "sparse", "offset", "dup", "onelabel", "dead", "bighead", "mlrows", "deadrelu", "bigmean")
 DEAD_BIAS = 64.0
 BIGHEAD = 200.0
 MLROWS_BIAS = -6.0
@@ -92,11 +97,13 @@ def edge_params(p, hp, conf, how):
     """State dict p changed `how` (a copy; the table-only transforms return it unchanged)."""
     assert how in HOWS, how
     q = {k: np.array(v, copy=True) for k, v in p.items()}
-    if how == "dead":
+    if how in ("dead", "deadrelu", "bigmean"):
         for i in range(len(conf)):
             b = q[f"fusion_layers.{i}.0.bias"]
-            b[0::3] = F32(-DEAD_BIAS)
-            b[1::3] = F32(DEAD_BIAS)
+            if how != "bigmean":
+                b[0::3] = F32(-DEAD_BIAS)
+            if how != "deadrelu":
+                b[1::3] = F32(DEAD_BIAS)
     elif how == "bighead":
         assert hp.loss_mode == 0, "bighead saturates a sigmoid head: that is the status tests' subject"
         q["central_classifier.weight"] = (q["central_classifier.weight"] * F32(BIGHEAD)).astype(F32)
@@ -109,7 +116,8 @@ def edge_params(p, hp, conf, how):
 
 def dead_columns(conf, hp, cell=0):
     """Columns of `cell` that 'dead' leaves with batch variance exactly 0: a ReLU's r = 0 mod 3 (the activation is 0 on every
-    row) and a sigmoid's r = 1 mod 3 (it rounds to 1 on every row, in float32 and in float64).  A LeakyReLU cell has none."""
+    row) and a sigmoid's r = 1 mod 3 (it rounds to 1 on every row, in float32 and in float64).  A LeakyReLU cell has none.
+    'deadrelu' leaves a ReLU cell the same r = 0 mod 3 columns (and a sigmoid cell none: its r = 0 mod 3 columns are e^-64, not 0)."""
     nl = int(conf[cell][2])
     cols = np.arange(hp.R)
     return cols[cols % 3 == 0] if nl == 0 else (cols[cols % 3 == 1] if nl == 1 else cols[:0])

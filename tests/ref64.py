@@ -16,6 +16,8 @@ Magnitudes:
   * activation         M_a = slope * M_y + c |a|        (ReLU slope 1, c 0; LeakyReLU 1, 1; Sigmoid 1/4, 4: its own rounding)
   * BN (eval)          M_z = |gamma| * rstd * (M_a + |running_mean|) + |beta| + |z|
   * BN (train)         as eval with the batch mean, plus the batch-mean term mean_b(M_a) and the variance's share
+  * batch sums (opt.)  batch_sum_term=True: M_mu = mean_b(M_a) + (n - 1) mean_b|a| and M_var += (n - 1) var, the rounding of the two
+                       n-term float32 sums themselves at the depth of a serial sum (sound for any order); off by default, see forward()
   * dropout            M_z * keep * scale
   * weight gradients   M_dW = M_dy^T @ M_x              (the spec's |dy|^T |a|, with forward errors carried in M_x)
 An element at an activation kink (|y| within the bound of 0) may take either branch: its gradient gets an O(1) allowance.
@@ -42,8 +44,19 @@ def _sig(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
-def forward(params, conf, hp: "O.Hyper", feats, train: bool, seed: int = 0, step: int = 0):
-    """Returns (logits, M_logits, cache); feats: s0..s3 / v0..v3 (rows, width) as the values the engine reads (dequantised)."""
+def forward(params, conf, hp: "O.Hyper", feats, train: bool, seed: int = 0, step: int = 0, batch_sum_term: bool = False):
+    """Returns (logits, M_logits, cache); feats: s0..s3 / v0..v3 (rows, width) as the values the engine reads (dequantised).
+    batch_sum_term (train mode under BatchNorm only): M_mu = mean_b(M_a) counts the errors of the summed values, not the rounding of
+    the batch sum itself.  Each of the n - 1 additions of a serial float32 sum rounds a partial sum of at most sum_b|a|, so the mean
+    carries up to (n - 1) 2^-24 mean_b|a| more; a column whose values all lie near one number D (a ReLU behind a bias of +D,
+    identical rows) has nothing else in M_mu of that size.  With the flag M_mu gains (n - 1) mean_b|a|, and M_var, M_xhat, the
+    running mean's M and the backward follow from it.  n - 1 is the depth of a serial sum (how the numpy oracle adds rows), an
+    upper bound for every summation order; the engine's own order is shallower.
+    The batch variance's own sum has the analogous term: n non-negative terms (a - mu)^2 of mean var, each addition rounding a
+    partial sum of at most n var, so M_var gains (n - 1) var.  It is KEPT, as part of the same flag.  The value-domain entries of
+    tests/test_inputs_cpu.py calibrate without it (the float32 oracle's running statistics at 0.44 .. 0.83 of the allowed 1.0 on
+    every flagged entry); the learning rate of 3e-2 in tests/test_axes_cpu.py does not: with the mean's term alone one of its
+    twelve populations stays at 1.33 on a running variance, with both every one is at 0.60 or below (figures in that file)."""
     L = len(conf)
     cells = []
     out = M_out = None
@@ -87,7 +100,11 @@ def forward(params, conf, hp: "O.Hyper", feats, train: bool, seed: int = 0, step
                 rstd = 1.0 / np.sqrt(var + hp.bn_eps)
                 xhat = d * rstd
                 Mmu = Ma.mean(0)
+                if batch_sum_term:
+                    Mmu = Mmu + (n - 1.0) * np.abs(a).mean(0)
                 Mvar = 2.0 * (np.abs(d) * (Ma + Mmu)).mean(0) + var
+                if batch_sum_term:
+                    Mvar = Mvar + (n - 1.0) * var
                 # xhat = d * rstd: d's error (M_a + M_mu) and rstd's relative error (half the variance's)
                 Mxhat = rstd * (Ma + Mmu) + np.abs(xhat) * (0.5 * Mvar / (var + hp.bn_eps)) + np.abs(xhat)
                 c.update(mu=mu, var=var, rstd=rstd, xhat=xhat, Mxhat=Mxhat, Mmu=Mmu, Mvar=Mvar, n=n, g=g)
@@ -370,17 +387,18 @@ def adam_step64(w, m, v, g, Mg, scalars, hp: "O.Hyper", tau_v=1.0, m_new=None, v
     return (m1, Mm), (v1, Mv), (w - dw, np.abs(w) + np.abs(dw) + UNDERFLOW / U)
 
 
-def train_step64(state, conf, hp: "O.Hyper", batch, seed, step, eta, t, tau_logits, tau_v, observed=None, pos_weight=None):
+def train_step64(state, conf, hp: "O.Hyper", batch, seed, step, eta, t, tau_logits, tau_v, observed=None, pos_weight=None,
+                 batch_sum_term=False):
     """One train step of one candidate in float64.  state = {"w": state dict (parameters and BN running statistics), "m": ..,
     "v": ..} is the float32 state before the step; batch holds the rows of this step in batch order (taps, label, and vlogit /
     slogit / multilabel where the head uses them): its length is the step's nvalid.  seed / step select the dropout masks (step =
     the global 0-based step), eta is this step's learning rate and t the 1-based Adam step.  observed = {"m": .., "v": ..}: the
-    moments the implementation wrote, on which the expected parameters are evaluated.
+    moments the implementation wrote, on which the expected parameters are evaluated.  batch_sum_term: as in forward().
     Returns {"m" / "v" / "w" / "runstat": {key: (expected, M)}, "loss": (sum over the rows, bound), "count": (lo, hi)}."""
     P = state["w"]
     n = len(batch["label"])
     feats = {k: a for k, a in batch.items() if k not in ("label", "multilabel")}
-    lg, Ml, cache = forward(P, conf, hp, feats, True, seed=seed, step=step)
+    lg, Ml, cache = forward(P, conf, hp, feats, True, seed=seed, step=step, batch_sum_term=batch_sum_term)
     if hp.loss_mode == 1:
         pw = np.ones(hp.C) if pos_weight is None else _f(pos_weight)
         dl, Mdl = bce_dlogits(lg, Ml, batch["multilabel"], pw, n, hp.C, tau_logits)

@@ -6,9 +6,10 @@
   the per-tap, the resident and the wide sweep and of k_eval;
 * plain cells (allow_plain_cell, bn = 0, drpt = 0: a cell is [Linear, nl]) on every chain family: lean, resident, the general
   chain at 1 / 2 / 4 m-blocks, same-group, chain_split, two-group, wide — and every dev-pass build of their geometries;
-* the hyper-parameter scalars (wd, beta1, beta2, adam_eps, bn_eps, bn_momentum, f1_threshold, the learning rates), three sets with
-  every field off its default, among them wd = 0, beta1 = 0, bn_momentum = 1 and learning rates of exactly 0 (w must come back
-  bit-identical while m and v move), on every train schedule, a wide population and the multi-label head's dev pass.
+* the hyper-parameter scalars (wd, beta1, beta2, adam_eps, bn_eps, bn_momentum, f1_threshold, the learning rates), four sets with
+  every field off its default, among them wd = 0, beta1 = 0, bn_momentum = 1, learning rates of exactly 0 (w must come back
+  bit-identical while m and v move) and eta_max = 3e-2, on every train schedule, a wide population and the multi-label head's dev
+  pass.  The steps of the 3e-2 set's populations alone are judged with ref64's batch_sum_term (test_axes_cpu.spec_flag).
 
 tests/test_axes_cpu.py holds the designs, the seeds and the inputs (shared by import) and keeps the float32 oracle under a quarter
 of every tau on exactly these inputs.  Same rule, same taus as the sibling files: |got - ref64| <= tau 2^-24 M elementwise
@@ -17,7 +18,7 @@ asserted by name with pop.schedule(), the resident one's k_president build with 
 
 Run on its own, with a time limit:  python -m pytest tests/test_gpu_axes_ref64.py -m gpu -x -q -s
 
-Observed on the MI355X (113 tests, 9 s; the run prints the table with -s): worst ratio per quantity, the engine's figure / the float32
+Observed on the MI355X (131 tests; the run prints the table with -s): worst ratio per quantity, the engine's figure / the float32
 oracle's on the same inputs on the CPU (tests/test_axes_cpu.py prints its own with -s).  No kernel or host code had to change.
 
   group              forward      fwd_train    backward     run_stats    train m      train v      train w      runstat      loss
@@ -28,6 +29,8 @@ oracle's on the same inputs on the CPU (tests/test_axes_cpu.py prints its own wi
   scalars sa         0.20 / 0.13  0.005/ 0.008 1.30 / 1.30  0.33 / 0.43  0.40 / 0.40  0.17 / 0.17  3.70 / 3.97  0.58 / 0.79  0.003 / 0.002
   scalars sb         0.14 / 0.14  0.006/ 0.008 1.30 / 1.30  0.36 / 0.44  0.85 / 0.83  0.20 / 0.20  3.56 / 3.76  0.59 / 0.69  0.004 / 0.004
   scalars sc         0.16 / 0.16  0.006/ 0.009 1.30 / 1.30  0.84 / 0.84  1.02 / 1.13  0.18 / 0.18  0 / 0        0.95 / 0.95  0.002 / 0.002
+  scalars sd *       0.12 / 0.14  0.005/ 0.006 1.30 / 1.30  0.64 / 0.65  0.88 / 0.89  0.19 / 0.19  3.97 / 4.03  0.80 / 0.80  0.002 / 0.001
+  (* the population columns, train m .. loss, with batch_sum_term; the four entry-point columns without)
   (the first four columns of a scalar set are its SCALAR_EVAL_CASES, the others its populations; the eval forward's engine figure
    covers every MFAS_EVAL_NO_* build and row range, the oracle's one pass over the 83 rows)
   dev_loss_sum of the one-epoch calls: 0.013 (CE), 0.050 (multi-label) of its bound.
@@ -162,7 +165,7 @@ def test_population_steps_vs_ref64(dev, spec):
     per = ehp.order_per_candidate
     for k, c in enumerate(confs):
         GT.check_candidate(S, ST, k, c, hp, p0s[k], inp["t"], inp["order"][k] if per else inp["order"], inp["seeds"][k], inp["etas"],
-                           f"{pid} cand {k}", rec)
+                           f"{pid} cand {k}", rec, batch_sum_term=AX.spec_flag(spec))
     if not inp["etas"].any():
         for k, c in enumerate(confs):
             for j in (1, 2, 3):

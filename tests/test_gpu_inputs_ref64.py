@@ -9,16 +9,21 @@ elementwise (logits 6, gradients 20, running statistics 4; steps: m 20, v 1, w 2
 
 * status is 0 and every reported loss finite: these inputs are finite in the reference's float32 formula;
 * 'onelabel': a count equals ref64's lo whenever lo == hi;
-* 'dup' / 'dead' with BatchNorm: a named column has batch variance 0 in ref64's own forward (so the case cannot silently stop
-  being degenerate); its running variance moves by exactly the momentum step towards 0, which the elementwise check holds;
-* POP_CASES: one candidate of a population transformed ('dead', 'bighead'), on the resident schedule, on chain_split and on
-  launch per phase: the neighbours bit-identical to the run where nobody is transformed, the transformed one held to ref64.
+* 'dup' / 'dead' / 'deadrelu' with BatchNorm: a named column has batch variance 0 in ref64's own forward (so the case cannot
+  silently stop being degenerate; 'deadrelu': a column of the FIRST cell, a ReLU, exactly 0 on every row); its running variance moves
+  by exactly the momentum step towards 0, which the elementwise check holds;
+* 'bigmean' and the wide 'dup' (test_inputs_cpu.FLAGGED) are judged with ref64's batch_sum_term — the rounding of the two batch sums
+  themselves added to M_mu and M_var (tests/ref64.py::forward) — in forward_train, backward and the train steps; every other entry,
+  'deadrelu' included, without it.  The taus are the same;
+* POP_CASES: one candidate of a population transformed ('dead', 'bighead', 'deadrelu'), on the resident schedule, on chain_split, on
+  the same-group launch and on launch per phase: the neighbours bit-identical to the run where nobody is transformed, the
+  transformed one held to ref64 (without the term).
 
 tests/test_inputs_cpu.py holds the float32 oracle under a quarter of each tau on exactly these inputs.
 
 Run on its own, with a time limit:  python -m pytest tests/test_gpu_inputs_ref64.py -m gpu -x -q -s
 
-Observed on the MI355X (39 tests, 8 s; the run prints the table with -s): worst ratio per quantity and transform, the engine's
+Observed on the MI355X (54 tests, 8 s; the run prints the table with -s): worst ratio per quantity and transform, the engine's
 figure / the float32 oracle's on the same inputs on the CPU (tests/test_inputs_cpu.py).  No kernel had to change.
 
   transform   forward      fwd_train    backward     run_stats    train m      train v      train w      runstat      loss
@@ -32,9 +37,17 @@ figure / the float32 oracle's on the same inputs on the CPU (tests/test_inputs_c
   dead        0.53 / 0.51  0.59 / 0.74  3.02 / 3.02  0.77 / 0.77  0.79 / 0.79  0.18 / 0.17  3.49 / 3.66  0.81 / 0.81  0.010 / 0.004
   bighead     0.24 / 0.17  0.09 / 0.14  2.49 / 3.46  0.80 / 0.80  0.86 / 0.86  0.18 / 0.18  3.96 / 4.13  0.76 / 0.76  0.002 / 0.002
   mlrows      0.31 / 0.17  0.27 / 0.32  2.05 / 2.50  0.60 / 0.60  0.92 / 0.92  0.18 / 0.18  4.12 / 4.12  0.79 / 0.79  0.006 / 0.002
+  deadrelu    0.11 / 0.05  0.000/ 0.000 2.20 / 2.20  0.80 / 0.80  0.85 / 0.87  0.17 / 0.17  3.42 / 3.92  0.83 / 0.82  <0.001/ <0.001
+  bigmean *   0.63 / 0.58  0.004/ 0.008 1.45 / 1.45  0.81 / 0.81  0.73 / 0.73  0.17 / 0.17  3.92 / 3.65  0.82 / 0.82  <0.001/ <0.001
+  (* with batch_sum_term.  The two rows are the four narrow entries each; the wide w65 entries, engine (candidate 0's single passes,
+   all three candidates' steps) / oracle (all three candidates):
+   w65 deadrelu   0.02 / 0.05  0.000/ 0.009 0.57 / 1.58  0.78 / 0.78  0.77 / 0.77  0.15 / 0.16  3.17 / 3.41  0.82 / 0.80  <0.001/ <0.001
+   w65 bigmean *  0.02 / 0.62  0.000/ 0.023 0.57 / 1.58  0.78 / 0.78  0.51 / 0.51  0.16 / 0.16  2.70 / 2.85  0.81 / 0.78  <0.001/ <0.001
+   w65 dup *      0.04 / 0.11  0.001/ 0.111 0.57 / 1.58  0.74 / 0.74  0.78 / 0.79  0.16 / 0.17  3.04 / 2.90  0.82 / 0.80  <0.001/ <0.001)
   (the wide case, w256 'bighead', is inside the 'bighead' row of the oracle's column; the engine's own: forward 0.03, fwd_train
    0.02, backward 1.65, m 0.82, v 0.17, w 3.85, loss 0.002; it has no BatchNorm)
-  one transformed candidate (dead / bighead): m 0.0001 / 0.73, v 0.00004 / 0.17, w 0.98 / 3.20, runstat 0.82 / 0.76, loss < 0.001
+  one transformed candidate (dead / bighead / deadrelu): m 0.0001 / 0.73 / 0.83, v 0.00004 / 0.17 / 0.17, w 0.98 / 3.20 / 3.20,
+  runstat 0.82 / 0.76 / 0.79, loss < 0.001
   dev_loss_sum of the one-epoch calls: 0.013 (CE), 0.003 (multi-label) of its bound.
 The eval forward's engine figure covers every MFAS_EVAL_NO_* build and row range, the oracle's one pass over the 83 rows.
 """
@@ -59,6 +72,10 @@ def zero_variance_column(how, conf, hp, cache):
     """(cell, column) that `how` leaves without batch variance, asserted on ref64's own forward."""
     if how == "dup":
         cell, col = 0, 0
+    elif how == "deadrelu":     # the FIRST cell, a ReLU: exactly 0 on every row
+        assert int(conf[0][2]) == 0, conf
+        cell, col = 0, int(IE.dead_columns(conf, hp, 0)[0])
+        assert cache["cells"][0]["var"][col] == 0.0 and not cache["cells"][0]["a"][:, col].any()
     else:
         cell = next(i for i in range(len(conf)) if int(conf[i][2]) in (0, 1))
         col = int(IE.dead_columns(conf, hp, cell)[0])
@@ -100,6 +117,7 @@ def test_input_values_vs_ref64(dev, i):
     cid, how, dtype = TI.INPUT_CASES[i]
     case = TI.base_case(cid)
     edit = TI.make_edit(how)
+    flag = TI.entry_flag(i)         # ref64's batch-sum term, for the entries that declare it
     hp = G.case_hyper(case)
     seed = TI.entry_seed(i)
     conf, p00 = G.case_params(case, hp, seed)
@@ -124,11 +142,11 @@ def test_input_values_vs_ref64(dev, i):
         # 2. forward_train + running statistics, backward
         pop.set_state_dict(0, p0)
         got_state = None
-        if hp.bn and how in ("dup", "dead"):
+        if hp.bn and how in ("dup", "dead", "deadrelu"):
             pop.forward_train(0, tab, 0, hp.B, step=3)
             got_state = G.state_np(pop)
             pop.set_state_dict(0, p0)
-        cache = G.check_train_passes(pop, dev, hp, conf, p0, t, tab, seed, tag, how)
+        cache = G.check_train_passes(pop, dev, hp, conf, p0, t, tab, seed, tag, how, batch_sum_term=flag)
         if got_state is not None:
             check_zero_variance(how, conf, hp, p0, cache, got_state, tag)
         # 3. one epoch of train() with a dev table
@@ -158,7 +176,7 @@ def test_input_values_vs_ref64(dev, i):
         for name in ST[j].dtype.names:
             if "loss" in name:
                 assert np.isfinite(ST[j][name]).all(), (tag, j, name)
-    GT.check_candidate(S, ST, 0, conf, hp, p0, ts, order, seed, etas, tag, how)
+    GT.check_candidate(S, ST, 0, conf, hp, p0, ts, order, seed, etas, tag, how, batch_sum_term=flag)
     if how == "onelabel" and hp.loss_mode == 0:
         for j in (1, 2, 3):
             batch, ep = GT.batch_of(ts, order, hp.B, j)
@@ -177,6 +195,7 @@ def test_wide_input_values_vs_ref64(dev, i):
     cid, how, dtype = TI.INPUT_CASES[i]
     case = TI.base_case(cid, dtype)
     edit = TI.make_edit(how)
+    flag = TI.entry_flag(i)
     hp, ehp, seed, confs, p0s, seeds, pop = GW.setup(case, dev)
     tag = f"{TI.INPUT_IDS[i]} R{hp.R} C{hp.C} B{hp.B}"
     bc = GW.base_case(case)
@@ -187,7 +206,15 @@ def test_wide_input_values_vs_ref64(dev, i):
         for k in range(GW.K):
             pop.set_state_dict(k, p0e[k])
         G.check_eval_forward(pop, hp, confs[0], p0e[0], t, tab, tag, f"wide_{how}")
-        G.check_train_passes(pop, dev, hp, confs[0], p0e[0], t, tab, seed, tag, f"wide_{how}", drop_seed=seeds[0])
+        got_state = None
+        if hp.bn and how in ("dup", "deadrelu"):
+            pop.forward_train(0, tab, 0, hp.B, step=3)
+            got_state = G.state_np(pop, 0)
+            pop.set_state_dict(0, p0e[0])
+        cache = G.check_train_passes(pop, dev, hp, confs[0], p0e[0], t, tab, seed, tag, f"wide_{how}", drop_seed=seeds[0],
+                                     batch_sum_term=flag)
+        if got_state is not None:
+            check_zero_variance(how, confs[0], hp, p0e[0], cache, got_state, tag)
         for k in range(GW.K):
             pop.set_state_dict(k, p0e[k])
         ntr = GT.train_rows(hp.B)
@@ -198,7 +225,7 @@ def test_wide_input_values_vs_ref64(dev, i):
             G.check_dev(stats[k:k + 1], G.state_np(pop, k), confs[k], hp, t, f"{tag} cand {k} train E=1")
     finally:
         pop.close()
-    GW.run_train_steps(dev, case, "shared", 1, (1, 2, 3), rec=f"wide_{how}", edit=edit)
+    GW.run_train_steps(dev, case, "shared", 1, (1, 2, 3), rec=f"wide_{how}", edit=edit, batch_sum_term=flag)
 
 
 # ------------------------------------------------------------------------------------------------ one transformed candidate among normal ones

@@ -230,15 +230,16 @@ def check_eval_forward(ep, hp, conf, p0, t, tab, tag, rec, env=None, k=0):
                 assert lo <= corr <= hi, f"{tag} forward F1 sum rows {row0}+{nrows} {env}: {corr} not in [{lo}, {hi}]"
 
 
-def check_train_passes(pop, dev, hp, conf, p0, t, tab, seed, tag, rec, k=0, drop_seed=None, tau_runstat=None):
+def check_train_passes(pop, dev, hp, conf, p0, t, tab, seed, tag, rec, k=0, drop_seed=None, tau_runstat=None, batch_sum_term=False):
     """forward_train of the first B rows (+ the running statistics it leaves) and backward of an arbitrary dL/dlogits, candidate k
-    against ref64.  Returns ref64's cache of that forward."""
+    against ref64 (batch_sum_term: ref64.forward's).  Returns ref64's cache of that forward."""
     torch = _torch()
     nb = hp.B
     step = 3
     f = feats_of(t, 0, nb)
     got = pop.forward_train(k, tab, 0, nb, step=step).cpu().numpy()
-    lg, Ml, cache = R64.forward(p0, conf, hp, f, True, seed=seed if drop_seed is None else drop_seed, step=step)
+    lg, Ml, cache = R64.forward(p0, conf, hp, f, True, seed=seed if drop_seed is None else drop_seed, step=step,
+                                batch_sum_term=batch_sum_term)
     R64.assert_close64(got, lg, Ml, TAU_LOGITS, f"{tag} forward_train", record=f"forward_train/{rec}")
     if hp.bn:
         rs, Mrs = R64.running_stats(p0, hp, cache)

@@ -116,9 +116,9 @@ def engine_states(pop, tab, p0s, etas, order_t, steps=(1, 2, 3)):
     return S, ST
 
 
-def check_candidate(S, ST, k, conf, hp, p0, t, order_k, seed, etas, tag, rec, steps=(1, 2, 3)):
+def check_candidate(S, ST, k, conf, hp, p0, t, order_k, seed, etas, tag, rec, steps=(1, 2, 3), batch_sum_term=False):
     """Items 1-6 of one candidate for every step of `steps` (sorted, 1-based global steps), each from the engine's own state
-    after step - 1, and what a 0-step call must leave."""
+    after step - 1, and what a 0-step call must leave.  batch_sum_term: ref64.train_step64's."""
     assert tuple(steps) == tuple(sorted(set(steps))) and steps[0] >= 1, steps
     train_keys = O.trainable_keys(conf, hp)
     for key, a in S[0][k]["w"].items():                               # a 0-step call: parameters untouched, moments zero
@@ -131,7 +131,8 @@ def check_candidate(S, ST, k, conf, hp, p0, t, order_k, seed, etas, tag, rec, st
     for j in steps:
         batch, ep = batch_of(t, order_k, hp.B, j)
         prev, cur = S[j - 1][k], S[j][k]
-        exp = R64.train_step64(prev, conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, TAU_V, observed=cur, pos_weight=pw)
+        exp = R64.train_step64(prev, conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, TAU_V, observed=cur, pos_weight=pw,
+                                 batch_sum_term=batch_sum_term)
         loss = ST[j][k]["train_loss_sum"][ep] - ST[j - 1][k]["train_loss_sum"][ep]
         count = int(ST[j][k]["train_corrects"][ep] - ST[j - 1][k]["train_corrects"][ep])
         if hp.loss_mode == 1:       # the multi-label head keeps no train count (chain.hip.h: bce_rows)

@@ -175,9 +175,9 @@ def edit_inputs(edit, hp, confs, p0s, t, dtype):
     return [p for p, _ in out], out[0][1]
 
 
-def run_train_steps(dev, case, order_mode, full, steps, rec=None, edit=None):
+def run_train_steps(dev, case, order_mode, full, steps, rec=None, edit=None, batch_sum_term=False):
     """train(max_steps = j) of the case's K = 3 candidates, `steps` against ref64 (test_gpu_train_ref64's check) under the case's taus.
-    edit: the inputs changed before the engine and ref64 see them (tests/test_gpu_inputs_ref64.py)."""
+    edit: the inputs changed before the engine and ref64 see them (tests/test_gpu_inputs_ref64.py); batch_sum_term: ref64's."""
     torch = G._torch()
     cid, dtype = case[0], case[9]
     hp, ehp, seed, confs, p0s, seeds, pop = setup(case, dev, order_mode)
@@ -192,7 +192,7 @@ def run_train_steps(dev, case, order_mode, full, steps, rec=None, edit=None):
     with mock.patch.dict(GT.TAUS, case_taus(cid)[1]):      # (test_gpu_train_ref64's check reads its module's taus)
         for k in range(K):
             GT.check_candidate(S, ST, k, confs[k], hp, p0s[k], t, order[k] if ehp.order_per_candidate else order, seeds[k], etas,
-                               f"{cid} {order_mode} cand {k}", rec or f"wide/{dtype}", steps)
+                               f"{cid} {order_mode} cand {k}", rec or f"wide/{dtype}", steps, batch_sum_term=batch_sum_term)
 
 
 @pytest.mark.gpu

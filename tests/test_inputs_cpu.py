@@ -15,15 +15,22 @@ base); on 7100 every condition holds for every case.
 The ambiguity condition is held on the eval pass of every case and on every train step, except where no seed can meet it
 (ambiguity_exempt): under train-mode BatchNorm ref64's magnitude grows by about rstd per cell, so the four BatchNorm cells of r16b
 (on the untransformed inputs too) and the transforms that take a batch variance towards 0 ('dup', 'offset', 'dead') under
-BatchNorm leave most rows of a train batch ambiguous on every seed (test_ambiguity_exemptions_do_not_depend_on_the_seed;
+BatchNorm, 'deadrelu' and 'bigmean' with them, leave most rows of a train batch ambiguous on every seed (test_ambiguity_exemptions_do_not_depend_on_the_seed;
 DESIGN.md section 8).  Three entries needed another draw to meet it (SEED_OVERRIDE); r65a-scaled and the wide w65-tiny met it on
 none of 60 seeds and were replaced by r32a-scaled and the wide w256-bighead.
 
 DEAD_BIAS (tests/input_edges.py) = 64, calibrated here.  Its size is not what limits it: a first cell with a ReLU and a bias of
 +D brings the oracle to 1.1 .. 2.0 on the running mean at D = 8, 16 and 64 alike (the float32 batch sum of n values near D carries a
 rounding of its own that ref64's M_mu does not count), so the BatchNorm cases of 'dead' have a sigmoid first cell (r16b, r129a,
-r17b; their later ReLU cells are dead too), where 64 keeps the margin; r32a / r65a / r256a / r16a do not, at any D.  Likewise
-'dup' on the wide case w65 (64-row batches) reaches 5.1 on the train running statistics and is not in the design.
+r17b; their later ReLU cells are dead too), where 64 keeps the margin; r32a / r65a / r256a / r16a do not, at any D.
+
+'dead' conflates two things, and only one of them needs that rounding counted.  'deadrelu' (the -64 half alone) keeps the margin
+under the unchanged ref64 on a ReLU FIRST cell under BatchNorm, and runs so: the lean chain (l16c, resident at one candidate), the
+general chain at 4, 2 and 1 m-blocks (r16a, r32a, r256a: also R >= 256) and the wide path (w65).  'bigmean' (the +64 half alone) on
+the same five bases, and 'dup' on the wide w65 (64 identical rows: 2.19 / 3.87 on the running statistics without it), are judged
+with ref64's batch_sum_term (FLAGGED; tests/ref64.py::forward derives it), under the same taus.  What the term costs is measured in
+test_batch_sum_term_only_loosens_and_by_at_most_n, what the flagged entries still see in
+test_value_mutations_on_the_split_dead_transforms.  l16c is a base case of this file alone (EXTRA_CASES says why).
 """
 import contextlib
 from unittest import mock
@@ -56,8 +63,30 @@ INPUT_CASES = [
     ("r16a", "bighead", B16), ("r33a", "bighead", F), ("r256a", "bighead", H), ("r65b", "bighead", F),
     ("r17a", "mlrows", H), ("r80a", "mlrows", F), ("r129b", "mlrows", B16),
     ("w256", "bighead", H),
+    # a ReLU FIRST cell under BatchNorm in every one: the two halves of 'dead' apart, and identical rows on the wide path
+    ("l16c", "deadrelu", F), ("r16a", "deadrelu", B16), ("r32a", "deadrelu", H), ("r256a", "deadrelu", F), ("w65", "deadrelu", H),
+    ("l16c", "bigmean", B16), ("r16a", "bigmean", H), ("r32a", "bigmean", F), ("r256a", "bigmean", B16), ("w65", "bigmean", B16),
+    ("w65", "dup", F),
 ]
 INPUT_IDS = [f"{c}-{how}-{ {F: 'f32', B16: 'bf16', H: 'f16'}[dt]}" for c, how, dt in INPUT_CASES]
+
+
+# Entries judged with ref64's batch_sum_term (tests/ref64.py::forward): a column of n values near one number, whose float32 batch
+# sum rounds by more than M_mu = mean(M_a) counts.  'deadrelu' needs none (a column of exact zeros sums exactly).
+def flagged(cid, how):
+    return how == "bigmean" or (how == "dup" and cid == "w65")
+
+
+FLAGGED = {i for i, (c, how, dt) in zip(INPUT_IDS, INPUT_CASES) if flagged(c, how)}
+
+# Base cases of this file alone, where neither CASES nor WIDE_CASES has what a family needs.  The lean chain (one row block, at
+# most two m-blocks, C <= 64) has two BatchNorm cases there: r16b, whose first cell is a sigmoid, and r1a, whose single column
+# leaves 'bigmean' nothing to set (R = 1 has no r = 1 mod 3).  (r16a, B = 33, runs the general chain at four m-blocks.)
+EXTRA_CASES = {"l16c": ("l16c", 16, 17, 20, G.W_B, [[1, 0, 0], [0, 2, 1]], True, 0.5, "")}
+
+
+def entry_flag(i):
+    return INPUT_IDS[i] in FLAGGED
 
 
 def is_wide(cid):
@@ -69,7 +98,7 @@ def base_case(cid, dtype=None):
     if is_wide(cid):
         c = GW.WIDE_CASES[GW.WIDE_IDS.index(cid)]
         return c[:9] + (dtype or c[9],)
-    return G.CASES[G.CASE_IDS.index(cid)]
+    return EXTRA_CASES[cid] if cid in EXTRA_CASES else G.CASES[G.CASE_IDS.index(cid)]
 
 
 # Entries whose draw at INPUT_SEED0 + i leaves more than a quarter of a train batch ambiguous: the first seed from 7200 on at which
@@ -84,8 +113,9 @@ def entry_seed(i):
 def ambiguity_exempt(cid, how, hp):
     """Train steps on which no seed can bring ref64's count interval under a quarter of the batch: under train-mode BatchNorm
     its magnitude grows by about rstd per cell, so the four BatchNorm cells of r16b (on the untransformed inputs too), and the
-    transforms that take a column's batch variance towards 0 ('dup', 'offset', 'dead': rstd up to 1 / sqrt(eps) = 316)."""
-    return hp.bn and (cid == "r16b" or how in ("dup", "offset", "dead"))
+    transforms that take a column's batch variance towards 0 ('dup', 'offset', 'dead', 'deadrelu': rstd up to 1 / sqrt(eps) =
+    316) or that are judged with the batch-sum term ('bigmean': M_mu of the +64 columns is 64 (n - 1))."""
+    return hp.bn and (cid == "r16b" or how in ("dup", "offset", "dead", "deadrelu", "bigmean"))
 
 
 def make_edit(how):
@@ -120,10 +150,23 @@ def check_inputs_conditions(conf, hp, p, t, tag):
     return amb
 
 
+def assert_first_cell_column_is_dead(conf, hp, p, t, tag):
+    """'deadrelu': the first cell is a ReLU and its first r = 0 mod 3 column is exactly 0 on every row of the first batch, batch
+    variance exactly 0, in ref64's own train-mode forward."""
+    assert hp.bn and int(conf[0][2]) == 0, tag
+    col = int(IE.dead_columns(conf, hp, 0)[0])
+    c = R64.forward(p, conf, hp, G.feats_of(t, 0, min(hp.B, len(t["label"]))), True)[2]["cells"][0]
+    assert c["var"][col] == 0.0 and not c["a"][:, col].any() and (c["y"][:, col] < -DEAD_MARGIN).all(), (tag, col, c["var"][col])
+
+
+DEAD_MARGIN = 32.0      # a dead column's pre-activations lie below -32: far from the kink, on every row
+
+
 def entry_ratios(i):
     """All nine quantities of INPUT_CASES[i] for the float32 oracle, on the GPU test's inputs; also asserts the input conditions."""
     cid, how, dtype = INPUT_CASES[i]
     edit = make_edit(how)
+    flag = entry_flag(i)
     counts = []
     real = R64.train_step64
 
@@ -135,6 +178,8 @@ def entry_ratios(i):
     def checked(conf, hp, p0, t, dt):
         p, t2 = edit(conf, hp, p0, t, dt)
         check_inputs_conditions(conf, hp, p, t2, INPUT_IDS[i])
+        if how == "deadrelu" and (not is_wide(cid) or conf.tolist() == base_case(cid)[5]):
+            assert_first_cell_column_is_dead(conf, hp, p, t2, INPUT_IDS[i])
         return p, t2
 
     with mock.patch.object(R64, "train_step64", spy):
@@ -143,13 +188,15 @@ def entry_ratios(i):
             seed = GW.SEED0 + GW.WIDE_IDS.index(cid)
             worst = {}
             for k, cells in enumerate(GW.case_confs(case)):
-                r = wide_oracle_case(case, k, cells, edit=checked)
-                r.update({"train_" + q: v for q, v in oracle_train_steps(GW.base_case(case, cells), dtype, seed=seed, edit=checked).items()})
+                r = wide_oracle_case(case, k, cells, edit=checked, batch_sum_term=flag)
+                r.update({"train_" + q: v for q, v in oracle_train_steps(GW.base_case(case, cells), dtype, seed=seed, edit=checked,
+                                                                           batch_sum_term=flag).items()})
                 worst = {q: max(worst.get(q, 0.0), v) for q, v in r.items()}
         else:
             case = base_case(cid)
-            worst = oracle_case(case, dtype, seed=entry_seed(i), edit=checked)
-            worst.update({"train_" + q: v for q, v in oracle_train_steps(case, dtype, seed=entry_seed(i), edit=checked).items()})
+            worst = oracle_case(case, dtype, seed=entry_seed(i), edit=checked, batch_sum_term=flag)
+            worst.update({"train_" + q: v for q, v in oracle_train_steps(case, dtype, seed=entry_seed(i), edit=checked,
+                                                                           batch_sum_term=flag).items()})
     for (lo, hi), n, hp in counts:
         assert ambiguity_exempt(cid, how, hp) or 4 * ambiguous_rows(lo, hi, n, hp) <= max(n, 4), (INPUT_IDS[i], "ambiguous rows in a train step", lo, hi, n)
     return worst
@@ -167,6 +214,10 @@ def entry_ratios(i):
 #   dead         0.51    0.74    3.02    0.77    0.79    0.17    3.66    0.81   0.004
 #   bighead      0.17    0.14    3.46    0.80    0.86    0.18    4.13    0.76   0.002
 #   mlrows       0.17    0.32    2.50    0.60    0.92    0.18    4.12    0.79   0.002
+#   deadrelu     0.05    0.009   2.20    0.80    0.87    0.17    3.92    0.82   < 0.001
+#   bigmean      0.62    0.023   1.58    0.81    0.73    0.17    3.65    0.82   < 0.001      (judged with batch_sum_term)
+#   ('dup' with the wide w65 entry, judged with batch_sum_term: forward 0.11, the other columns as above; without the term that
+#    entry is at 2.19 on the running statistics and 3.87 on the train runstat)
 
 
 @pytest.mark.parametrize("i", range(len(INPUT_CASES)), ids=INPUT_IDS)
@@ -181,10 +232,12 @@ def test_input_cases_calibration_margin(i):
     assert r["train_count"] == 0.0, INPUT_IDS[i]
 
 
-@pytest.mark.parametrize("cid,how", [("r16b", None), ("r32a", "offset"), ("r65a", "dup"), ("r129a", "dead")])
+@pytest.mark.parametrize("cid,how", [("r16b", None), ("r32a", "offset"), ("r65a", "dup"), ("r129a", "dead"), ("r32a", "deadrelu"),
+                                     ("r32a", "bigmean")])
 def test_ambiguity_exemptions_do_not_depend_on_the_seed(cid, how):
     """Why ambiguity_exempt exempts what it does: on each of eight seeds ref64 leaves more than a quarter of the first full train
-    batch ambiguous — on the untransformed r16b, and on a BatchNorm case under each of 'offset', 'dup' and 'dead'."""
+    batch ambiguous — on the untransformed r16b, and on a BatchNorm case under each of 'offset', 'dup', 'dead', 'deadrelu' and
+    'bigmean' (the last with the batch-sum term, as its entries are judged; 8 .. 16 of 20 rows without it)."""
     case = base_case(cid)
     hp = G.case_hyper(case)
     assert ambiguity_exempt(cid, how, hp)
@@ -194,18 +247,20 @@ def test_ambiguity_exemptions_do_not_depend_on_the_seed(cid, how):
         if how:
             p, t = make_edit(how)(conf, hp, p, t, "float32")
         zero = {k: np.zeros_like(v) for k, v in p.items()}
-        lo, hi = R64.train_step64({"w": p, "m": zero, "v": zero}, conf, hp, t, seed, 0, 1e-3, 1, G.TAU_LOGITS, GT.TAU_V)["count"]
+        lo, hi = R64.train_step64({"w": p, "m": zero, "v": zero}, conf, hp, t, seed, 0, 1e-3, 1, G.TAU_LOGITS, GT.TAU_V,
+                                   batch_sum_term=flagged(cid, how))["count"]
         assert 4 * (hi - lo) > hp.B, (cid, how, seed, lo, hi)
 
 
 def test_input_cases_cover_the_design():
-    assert 30 <= len(INPUT_CASES) <= 40 and len(set(INPUT_CASES)) == len(INPUT_CASES)
+    # (nine transforms in at most 40 entries, before 'deadrelu' and 'bigmean'; eleven now, in proportion)
+    assert 30 <= len(INPUT_CASES) <= 48 and len(set(INPUT_CASES)) == len(INPUT_CASES)
     per = {how: [(base_case(c, dt), dt) for c, h, dt in INPUT_CASES if h == how] for how in IE.HOWS}
     for how, lst in per.items():
         assert len(lst) >= 3, how
         bn = [c[6] for c, _ in lst]
-        assert any(bn) and (not all(bn) or how in ("dup", "dead")), how
-        if how in ("dup", "dead"):
+        assert any(bn) and (not all(bn) or how in ("dup", "dead", "deadrelu", "bigmean")), how
+        if how in ("dup", "dead", "deadrelu", "bigmean"):
             assert sum(bn) >= 2, how
         assert {dt for _, dt in lst} == set(G.DTYPES), how
         lm1 = ["lm1" in c[8] for c, _ in lst]
@@ -217,12 +272,33 @@ def test_input_cases_cover_the_design():
     assert {"multitask", "alphas", "lm1"} <= extras
     assert ids & {"r17a", "r80a"}
     assert any(base_case(c)[1] >= 256 for c in ids) and any(is_wide(c) for c in ids)
-    assert all(is_wide(c) or c in G.CASE_IDS for c in ids)
+    assert all(is_wide(c) or c in G.CASE_IDS or c in EXTRA_CASES for c in ids)
+    # BatchNorm and a ReLU first cell in every entry of the two halves of 'dead' and in the wide 'dup'; every BatchNorm transcription
+    # under each half: the lean chain (resident at one candidate), the general chain at 1 / 2 / 4 m-blocks, R >= 256, the wide path
+    from tests.test_wide_cpu import plan
+    for how in ("deadrelu", "bigmean"):
+        mine = [(c, base_case(c)) for c, h, _ in INPUT_CASES if h == how]
+        assert all(bc[6] and bc[5][0][2] == 0 for _, bc in mine), how
+        narrow = [bc for c, bc in mine if not is_wide(c)]
+        plans = [plan(G.case_hyper(bc), [bc[5]]) for bc in narrow]
+        assert any(p[5] == 1 and p[0] == 1 for p in plans), how
+        general = {-(-bc[3] // 16) if bc[3] <= 32 else 4 for bc, p in zip(narrow, plans) if p[5] == 0}
+        assert general == {1, 2, 4}, (how, general)
+        assert any(bc[1] >= 256 for bc in narrow) and any(is_wide(c) and bc[3] == 64 for c, bc in mine), how
+        assert all((INPUT_IDS[i] in FLAGGED) == (how == "bigmean") for i, e in enumerate(INPUT_CASES) if e[1] == how), how
+    wdup = [i for i, e in enumerate(INPUT_CASES) if e[1] == "dup" and is_wide(e[0])]
+    assert wdup and all(base_case(INPUT_CASES[i][0])[6] and base_case(INPUT_CASES[i][0])[3] == 64 and entry_flag(i) for i in wdup)
+    assert FLAGGED == {INPUT_IDS[i] for i, e in enumerate(INPUT_CASES) if e[1] == "bigmean"} | {INPUT_IDS[i] for i in wdup}
+    for cid, bc in EXTRA_CASES.items():     # (a base case of this file is one the lean chain runs)
+        assert plan(G.case_hyper(bc), [bc[5]])[5] == 1 and cid not in G.CASE_IDS, cid
 
 
 # (schedule of test_gpu_train_ref64.TRAIN_SCHEDULES, transform of one candidate's parameters, that candidate): the resident
-# schedule, chain_split and launch per phase.  'dead' goes to a candidate whose first cell is a sigmoid.
-POP_CASES = [("persistent", "dead", 3), ("chain_split", "bighead", 1), ("lean_chain", "bighead", 2)]
+# schedule, chain_split and launch per phase.  'dead' goes to a candidate whose first cell is a sigmoid (its +64 half on a ReLU
+# first cell needs ref64's batch-sum term), 'deadrelu' to one whose first cell is a ReLU: on the resident schedule, chain_split, the
+# same-group launch of the general chain, and the lean chain launched per phase.
+POP_CASES = [("persistent", "dead", 3), ("chain_split", "bighead", 1), ("lean_chain", "bighead", 2),
+             ("persistent", "deadrelu", 0), ("chain_split", "deadrelu", 0), ("same_group", "deadrelu", 0), ("lean_chain", "deadrelu", 0)]
 
 
 @pytest.mark.parametrize("name,how,k", POP_CASES, ids=[f"{n}-{h}" for n, h, _ in POP_CASES])
@@ -233,6 +309,10 @@ def test_population_cases_calibration_margin(name, how, k):
     hp, conf = inp["hp"], inp["confs"][k]
     assert how != "dead" or int(conf[0][2]) == 1
     p = IE.edge_params(inp["p0s"][k], hp, conf, how)
+    if how == "deadrelu":
+        assert_first_cell_column_is_dead(conf, hp, p, GT.batch_of(inp["t"], inp["order"], hp.B, 1)[0], f"{name} {how}")
+        if name == "chain_split":
+            assert not hp.alphas and 113 <= hp.R <= 128 and hp.B <= 16
     r = oracle_steps(conf, hp, p, inp["t"], inp["order"], inp["etas"], inp["seeds"][k], (1, 2, 3), GT.TAUS, f"{name} {how}")
     for q, tau in GT.TAUS.items():
         assert r[q] * 4.0 <= tau, (name, how, q, r[q], tau)
@@ -242,7 +322,10 @@ def test_population_cases_calibration_margin(name, how, k):
 # ------------------------------------------------------------------------------------------------ mutations
 def forward32(params, conf, hp, feats, train, seed=0, step=0, masks=None, mut=""):
     """O.forward restated so that the batch statistics are in reach: mut = 'var_e2' (the batch variance as E[a^2] - mean^2 in
-    float32, clamped at 0), 'rstd_clamp' / 'var_floor' (rstd from a variance clamped to at least 1e-3 / 1e-6).  mut = '' is O.forward bit for bit."""
+    float32, clamped at 0), 'rstd_clamp' / 'var_floor' (rstd from a variance clamped to at least 1e-3 / 1e-6), 'var_clamp5' (the
+    batch variance itself clamped to at least 1e-5: rstd and the running variance both read it), 'rstd_var0' (a var == 0 shortcut:
+    xhat = 0 without eps), 'mean_bf16' (the batch mean stored in bfloat16), 'gate_bn' (the first cell's ReLU gate read from the
+    BatchNorm output instead of the activation).  mut = '' is O.forward bit for bit."""
     cache = {"cells": [], "conf": conf}
     out = None
     for i in range(len(conf)):
@@ -263,17 +346,25 @@ def forward32(params, conf, hp, feats, train, seed=0, step=0, masks=None, mut=""
             g, be = params[f"fusion_layers.{i}.2.weight"], params[f"fusion_layers.{i}.2.bias"]
             if train:
                 mu = a.mean(axis=0, dtype=F32)
+                if mut == "mean_bf16":
+                    mu = O.bf16_round(mu)
                 var = ((a - mu) ** 2).mean(axis=0, dtype=F32)
+                if mut == "var_clamp5":
+                    var = np.maximum(var, F32(1e-5))
                 if mut == "var_e2":
                     var = np.maximum((a * a).mean(axis=0, dtype=F32) - mu * mu, F32(0)).astype(F32)
                 vr = np.maximum(var, F32({"rstd_clamp": 1e-3, "var_floor": 1e-6}[mut])) if mut in ("rstd_clamp", "var_floor") else var
                 rstd = (F32(1.0) / np.sqrt(vr + F32(hp.bn_eps))).astype(F32)
+                if mut == "rstd_var0":
+                    rstd = np.where(var == 0, F32(0), rstd)
                 xhat = ((a - mu) * rstd).astype(F32)
                 c.update(mu=mu, var=var, rstd=rstd, xhat=xhat, n=a.shape[0])
             else:
                 rm, rv = params[f"fusion_layers.{i}.2.running_mean"], params[f"fusion_layers.{i}.2.running_var"]
                 xhat = ((a - rm) / np.sqrt(rv + F32(hp.bn_eps))).astype(F32)
             z = (xhat * g + be).astype(F32)
+            if mut == "gate_bn" and train and i == 0 and nl == 0:
+                c["a"] = z          # (O.backward gates a ReLU on the cached activation)
         if hp.use_dropout and train:
             keep = masks[i] if masks is not None else O.dropout_keep(seed, step, i, z.shape[0], hp.R, hp.drpt)
             scale = F32(1.0 / (1.0 - hp.drpt))
@@ -322,7 +413,7 @@ def patched(mut):
         return contextlib.nullcontext()
     if mut == "sig_naive":
         return mock.patch.object(O, "_sigmoid", sigmoid_naive)
-    if mut in ("var_e2", "rstd_clamp", "var_floor"):
+    if mut in ("var_e2", "rstd_clamp", "var_floor", "var_clamp5", "rstd_var0", "mean_bf16", "gate_bn"):
         return mock.patch.object(O, "forward", lambda *a, **kw: forward32(*a, mut=mut, **kw))
     return mock.patch.object(O, "ce_loss", ce_loss_mut(mut))
 
@@ -342,6 +433,20 @@ def train_ratios(cid, how, mut, extra_edit=None):
         edit = (lambda conf, hp, p0, t, dt: extra_edit(conf, hp, *inner(conf, hp, p0, t, dt), dt))
     with patched(mut):
         return oracle_train_steps(base_case(cid), dtype, seed=entry_seed(i), edit=edit)
+
+
+def train_ratios_at(i, transformed, mut):
+    """Steps 1..3 of the float32 oracle with mutation `mut` on INPUT_CASES[i] as the GPU test judges it (its seed, table dtype
+    and batch_sum_term), or, transformed False, on the same draw untransformed and judged without the term, as the files that run
+    the untransformed inputs judge them.  A wide entry: the case's own cells (candidate 0)."""
+    cid, how, dtype = INPUT_CASES[i]
+    edit = make_edit(how) if transformed else None
+    flag = transformed and entry_flag(i)
+    with patched(mut):
+        if is_wide(cid):
+            case = base_case(cid, dtype)
+            return oracle_train_steps(GW.base_case(case), dtype, seed=GW.SEED0 + GW.WIDE_IDS.index(cid), edit=edit, batch_sum_term=flag)
+        return oracle_train_steps(base_case(cid), dtype, seed=entry_seed(i), edit=edit, batch_sum_term=flag)
 
 
 def over(r):
@@ -422,6 +527,110 @@ def test_recorded_findings_about_the_asked_mutations():
     assert not under(train_ratios("r65a", None, "rstd_clamp"))
     assert under(train_ratios("r65a", "dup", "rstd_clamp"))
     assert under(train_ratios("r33a", "scaled", "no_rowmax"))
+
+
+# (mutation, base case, transform): the entries that split 'dead' in two, each judged as the GPU test judges it
+SPLIT_MUTATIONS = [("var_e2", c, "bigmean") for c in ("l16c", "r16a", "r32a", "r256a", "w65")] + [("var_clamp5", "r16a", "deadrelu")]
+
+
+@pytest.mark.parametrize("mut,cid,how", SPLIT_MUTATIONS, ids=[f"{m}-{c}-{h}" for m, c, h in SPLIT_MUTATIONS])
+def test_value_mutations_on_the_split_dead_transforms(mut, cid, how):
+    """As test_value_mutations_of_a_train_step, on the entry's own draw: under every tau on the untransformed inputs judged
+    without the batch-sum term, over a tau on the transformed ones judged as the GPU test judges them ('bigmean': with the term).
+    Worst ratios of the mutated float32 oracle, old -> new (the test prints them with -s):
+
+      var_e2      batch variance as E[a^2] - mean^2: a column of values near 64 with a spread of 1 loses the variance to the rounding
+                  of 4096.  The term loosens M_var (through M_mu and by (n - 1) var), and the mutation still leaves tau by x5 .. x28:
+                  l16c old runstat 0.69 -> bigmean 19.4    r16a 0.70 -> 22.6    r32a 0.83 -> 111.4    r256a 0.84 -> 79.4
+                  w65 (the wide path, 64 rows) 0.69 -> 23.0
+      var_clamp5  the batch variance clamped to at least 1e-5, for rstd and for the running variance alike
+                  r16a old runstat 3.13, loss 0.34 (inside tau 4 and 1, though not by the x4 of an unmutated oracle: the draw has a
+                  variance below 1e-5 of its own in one step) -> deadrelu 35.0 (a dead column's running variance must move by
+                  exactly the momentum step towards 0; the clamp leaves 1e-5 n / (n - 1) of it)
+    """
+    i = entry_index(cid, how)
+    old = train_ratios_at(i, False, mut)
+    new = train_ratios_at(i, True, mut)
+    print(f"\n{mut} {INPUT_IDS[i]}: old {({q: round(v, 3) for q, v in old.items()})}\n   new: {({q: round(v, 3) for q, v in new.items()})}")
+    assert under(old), (mut, cid, "fails on the untransformed inputs already", old)
+    assert under(train_ratios_at(i, True, "")), (cid, how, "the unmutated oracle")
+    assert over(new), (mut, cid, how, new)
+
+
+def test_recorded_findings_about_the_split_dead_mutations():
+    """Mutations proposed for 'deadrelu', 'bigmean' and the wide 'dup' that do not separate old from new inputs, measured with the
+    float32 oracle on the entries' own draws:
+
+    * the batch mean stored in bfloat16: it FAILS on the untransformed inputs of every base (runstat 1900 .. 14000: 2^-9 of a mean
+      against a bound of a few 2^-24), so nothing about 'bigmean' is needed to see it; with the term it still fails there (1700 ..
+      6300), i.e. the term costs no power against an error of that size;
+    * a var == 0 shortcut that sets xhat = 0 without eps: invisible on 'deadrelu' and on the wide 'dup' (and everywhere else).
+      With a zero-variance column a - mean is exactly 0, so xhat is 0 whatever rstd is, and the backward of a dead ReLU column is
+      gated off; rstd of such a column reaches no output.  What a zero-variance column does pin is the variance itself, through
+      the running variance: var_clamp5 above;
+    * var_clamp5 on the other 'deadrelu' bases (l16c, r32a, r256a, w65): it fails on their UNTRANSFORMED draws already (runstat 15
+      .. 38): a variance below 1e-5 occurs by itself in their three steps (the first 16 rows of r256a's table leave ten first-cell ReLU
+      columns at 0 on every row), so against this mutation those entries add dead columns 0, 3, 6, .. of the FIRST cell on
+      every batch and schedule, not a new kind of value; r16a's draw stays inside tau;
+    * the first cell's ReLU gate read from the BatchNorm output: fails on the untransformed inputs of every base (m 26 .. 1e15:
+      the sign of (a - mean) rstd gamma + beta has little to do with the sign of the pre-activation);
+    * var_e2 on 'deadrelu' (E[0] - 0^2 is exact) and on the wide 'dup' (w65: activations of about 1, the rounding of a^2 stays
+      inside the running variance's absolute allowance; r65a-dup above sees it): under every tau."""
+    dr, bm = entry_index("r16a", "deadrelu"), entry_index("r32a", "bigmean")
+    wd = next(i for i, e in enumerate(INPUT_CASES) if e[0] == "w65" and e[1] == "dup")
+    assert not under(train_ratios_at(bm, False, "mean_bf16")) and not under(train_ratios_at(bm, True, "mean_bf16"))
+    for i in (dr, wd):
+        assert under(train_ratios_at(i, True, "rstd_var0")) and under(train_ratios_at(i, True, "var_e2"))
+    for cid in ("l16c", "r32a", "r256a", "w65"):
+        assert not under(train_ratios_at(entry_index(cid, "deadrelu"), False, "var_clamp5")), cid
+    assert not under(train_ratios_at(dr, False, "gate_bn")) and not under(train_ratios_at(bm, False, "gate_bn"))
+
+
+# ------------------------------------------------------------------------------------------------ what the batch-sum term costs
+def batch_sum_term_cost():
+    """M with batch_sum_term over M without it, elementwise, on the UNTRANSFORMED base draw of every new entry (the first train
+    batch, dropout step 3, an arbitrary dL/dlogits): {quantity: ratios of all elements of all draws}."""
+    acc = {"forward_train": [], "gradients": [], "running_mean": [], "running_var": []}
+    for i, (cid, how, dtype) in enumerate(INPUT_CASES):
+        if how not in ("deadrelu", "bigmean") and not entry_flag(i):
+            continue
+        case, seed = (GW.base_case(base_case(cid, dtype)), GW.SEED0 + GW.WIDE_IDS.index(cid)) if is_wide(cid) else (base_case(cid), entry_seed(i))
+        hp = G.case_hyper(case)
+        conf, p = G.case_params(case, hp, seed)
+        f = G.feats_of(G.case_table(case, hp, G.N_EVAL, seed, dtype), 0, hp.B)
+        dl = (np.random.default_rng(seed).standard_normal((hp.B, hp.C)) / hp.B).astype(F32)
+        m = []
+        for flag in (False, True):
+            _, Ml, cache = R64.forward(p, conf, hp, f, True, seed=seed, step=3, batch_sum_term=flag)
+            m.append((Ml, R64.backward(p, hp, cache, dl)[1], R64.running_stats(p, hp, cache)[1]))
+        (Ml0, MG0, Mr0), (Ml1, MG1, Mr1) = m
+        acc["forward_train"].append((Ml1 / Ml0).ravel())
+        for k in MG0:       # (an element without any magnitude, a dropped unit's, has none with the term either)
+            assert not MG1[k][MG0[k] == 0].any(), (INPUT_IDS[i], k)
+            acc["gradients"].append((MG1[k][MG0[k] > 0] / MG0[k][MG0[k] > 0]).ravel())
+        acc["running_mean"] += [(Mr1[k] / Mr0[k]).ravel() for k in Mr0 if k.endswith("mean")]
+        assert all((Mr1[k] <= hp.B * Mr0[k]).all() for k in Mr0 if k.endswith("mean")), INPUT_IDS[i]
+        acc["running_var"] += [(Mr1[k] / Mr0[k]).ravel() for k in Mr0 if k.endswith("var")]
+    return {q: np.concatenate(v) for q, v in acc.items()}
+
+
+def test_batch_sum_term_only_loosens_and_by_at_most_n():
+    """The term only adds to M (no comparison tightens), and the running mean's M grows by less than the factor n: M_a >= |a|
+    for every nonlinearity, so (n - 1) mean|a| <= (n - 1) mean(M_a).  Measured, M with the term / M without, over the eleven
+    untransformed base draws (what a flagged comparison can still see is tau times these; the test prints them with -s):
+
+      quantity        worst      median
+      running mean    5.3        1.45
+      running var     2.6        1.34
+      forward_train   2.9        1.44
+      gradients       9.5e4      1.44     (the worst: fusion-bias gradients under BatchNorm, which cancel to a round-off-sized M)
+
+    An error of a few 2^-24 of a column's mean or variance, which the unflagged rule catches, can pass a flagged one; one of 2^-9 of
+    the mean or of the whole variance cannot (mean_bf16, var_e2, var_clamp5 above)."""
+    r = batch_sum_term_cost()
+    for q, a in r.items():
+        print(f"\nbatch_sum_term M ratio {q}: worst {a.max():.4g} median {np.median(a):.3g}")
+        assert np.isfinite(a).all() and (a >= 1.0).all(), q          # (the factor n on the running mean: asserted per draw)
 
 
 def big_shifted_head(conf, hp, p, t, dtype):

@@ -70,10 +70,10 @@ def test_bce_and_f1_match_the_oracle():
 
 
 # ------------------------------------------------------------------------------------------------ calibration on the GPU shapes
-def oracle_case(case, dtype, seed=None, edit=None):
+def oracle_case(case, dtype, seed=None, edit=None, batch_sum_term=False):
     """The float32 oracle and ref64 on exactly the inputs test_gpu_ref64 gives the engine: worst ratio per quantity.
     edit(conf, hp, p0, t, dtype) -> (p0, t): the parameters and the table changed before either side sees them
-    (tests/test_inputs_cpu.py)."""
+    (tests/test_inputs_cpu.py); batch_sum_term: ref64.forward's, for the train-mode pass."""
     hp = G.case_hyper(case)
     if seed is None:
         seed = 1000 + G.CASE_IDS.index(case[0]) if case[0] in G.CASE_IDS else 7
@@ -90,7 +90,7 @@ def oracle_case(case, dtype, seed=None, edit=None):
     f = G.feats_of(t, 0, nb)
     p32 = {k: v.copy() for k, v in p0.items()}
     lg32, cache32 = O.forward(p32, conf, hp, f, True, seed=seed, step=step)
-    lg, Ml, cache = R64.forward(p0, conf, hp, f, True, seed=seed, step=step)
+    lg, Ml, cache = R64.forward(p0, conf, hp, f, True, seed=seed, step=step, batch_sum_term=batch_sum_term)
     out["forward_train"] = R64.worst_ratio(lg32, lg, Ml)[0]
     rng = np.random.default_rng(seed)
     dl = (rng.standard_normal((nb, hp.C)) / nb).astype(F32)
@@ -328,7 +328,7 @@ def stale_taps(batch, stale):
     return {k: (stale[k][:n] if k[0] in "sv" and k[1:].isdigit() else v) for k, v in batch.items()}
 
 
-def oracle_steps(conf, hp, p0, t, order, etas, seed, steps, taus, tag, mut="", wrong=None):
+def oracle_steps(conf, hp, p0, t, order, etas, seed, steps, taus, tag, mut="", wrong=None, batch_sum_term=False):
     """The float32 oracle through steps 1..steps[-1] of one candidate (table t, sample order [EPOCHS][N], dropout seed), every
     step of `steps` checked against ref64 from the oracle's own state before it: worst ratio per quantity."""
     N = order.shape[1]
@@ -361,14 +361,15 @@ def oracle_steps(conf, hp, p0, t, order, etas, seed, steps, taus, tag, mut="", w
             seen = {k: v[idx] for k, v in t.items()}
         new, loss, count = oracle_step32(hist[-1], conf, hp, seen, seed, j - 1, eta_j, t_j, pw, m, stale)
         if j in steps:
-            exp = R64.train_step64(hist[-1], conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, GT.TAU_V, observed=new, pos_weight=pw)
+            exp = R64.train_step64(hist[-1], conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, GT.TAU_V, observed=new, pos_weight=pw,
+                                     batch_sum_term=batch_sum_term)
             r = R64.check_train_step(exp, new, loss, count, taus, f"{tag} step {j}", hard=False)
             worst = {q: max(worst.get(q, 0.0), r[q]) for q in r}
         hist.append(new)
     return worst
 
 
-def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False, N=None, steps=(1, 2, 3), edit=None):
+def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False, N=None, steps=(1, 2, 3), edit=None, batch_sum_term=False):
     """Steps of train() as test_gpu_train_ref64 sets them up (N rows: by default one full batch and the ragged one), the float32
     oracle checked step by step on `steps`: worst ratio per quantity.  edit: as in oracle_case."""
     hp = G.case_hyper(case)
@@ -380,7 +381,8 @@ def oracle_train_steps(case, dtype, mut="", seed=None, other_order=False, N=None
         p0, t = edit(conf, hp, p0, t, dtype)
     order = GT.make_order(N, seed)
     wrong = GT.make_order(N, seed, 2)[1]            # another candidate's order
-    return oracle_steps(conf, hp, p0, t, order, GT.step_etas(N, hp.B), seed, tuple(steps), GT.TAUS, case[0], mut, wrong)
+    return oracle_steps(conf, hp, p0, t, order, GT.step_etas(N, hp.B), seed, tuple(steps), GT.TAUS, case[0], mut, wrong,
+                        batch_sum_term=batch_sum_term)
 
 
 def test_train_case_dtypes_rotate():

@@ -21,9 +21,9 @@ F32 = np.float32
 
 
 # ------------------------------------------------------------------------------------------------ calibration
-def wide_oracle_case(case, k, cells, edit=None):
+def wide_oracle_case(case, k, cells, edit=None, batch_sum_term=False):
     """The float32 oracle and ref64 on the inputs test_gpu_wide_ref64 gives the engine for candidate k: worst ratio per quantity
-    (test_ref64_cpu.py::oracle_case for a batch that may be larger than the 83-row dev table; edit as there)."""
+    (test_ref64_cpu.py::oracle_case for a batch that may be larger than the 83-row dev table; edit and batch_sum_term as there)."""
     bc, dtype = GW.base_case(case, cells), case[9]
     hp = G.case_hyper(bc)
     seed = GW.SEED0 + GW.WIDE_IDS.index(case[0])
@@ -42,7 +42,7 @@ def wide_oracle_case(case, k, cells, edit=None):
         f = G.feats_of(tb, 0, nb)
         p32 = {kk: v.copy() for kk, v in p0.items()}
         lg32, cache32 = O.forward(p32, conf, hp, f, True, seed=seed + 3 * k, step=3)
-        lg, Ml, cache = R64.forward(p0, conf, hp, f, True, seed=seed + 3 * k, step=3)
+        lg, Ml, cache = R64.forward(p0, conf, hp, f, True, seed=seed + 3 * k, step=3, batch_sum_term=batch_sum_term)
         out["forward_train"] = max(out.get("forward_train", 0.0), R64.worst_ratio(lg32, lg, Ml)[0])
         rng = np.random.default_rng(seed + k)
         dl = (rng.standard_normal((nb, hp.C)) / nb).astype(F32)
