@@ -229,6 +229,20 @@ int mfas_population_set_profiling(mfas_population* pop, int32_t on);
  * AND the sweep of the same candidates, released cell by cell through per-cell flags); info[7] = candidates. */
 int mfas_population_schedule(const mfas_population* pop, int32_t info[8]);
 
+/* The kernel builds the LAST mfas_population_train / mfas_population_train_from call of this population launched, as the library
+ * recorded them where it made the launches: "k_step<1,1,4,0,1>:7 k_chain<1,0>:8 ..." — one item per distinct build, the kernel
+ * family with the instantiation's template arguments, a colon and the number of launches; items sorted by name, separated by one
+ * space, NUL-terminated, truncated to `cap`.  Families and their arguments: k_step<MB,NT,WPE,LEAN,NS>, k_step_same<MB,NT,NS>,
+ * k_chain<MB,LEAN>, k_chain_wide, k_sweep_wide<NT>, k_president<MB,NTR,X16,NU,PLAIN> (MB: 16-row batch tiles; NT: nontemporal W/m/v
+ * streaming; WPE: waves per SIMD the build is bounded for; LEAN: the R <= 16 chain; NS: workgroups per candidate chain; NTR: tiles
+ * per wave of a resident unit; X16: 16-bit staging; NU: units per resident workgroup; PLAIN: 0 general chain, 1 search default,
+ * 2 BatchNorm alone).  The name and the function pointer of a launch come from one template instantiation, so the record names
+ * what ran, not what the plan implies.  A call that is refused leaves the previous record; a call that passes its checks starts an
+ * empty one; a resident call that falls back to launch per phase keeps both parts.  The dev pass (k_eval), the packers and the
+ * single-batch entry points (forward_train / backward) are not recorded.  Tests use it to assert a build by name; no reference
+ * counterpart. */
+int mfas_population_launch_record(const mfas_population* pop, char* buf, int32_t cap);
+
 /* (new, round 3) The same decision WITHOUT creating a population — a pure query, nothing is allocated or launched: would
  * mfas_population_create(hp, confs, n_cells, ..., K, device, ..., chunk_cols) take the resident persistent schedule (every
  * chain and every feature unit resident on its own CU slot, W/m/v in registers, one launch per epoch)?  The host plans

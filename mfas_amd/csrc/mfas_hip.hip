@@ -115,6 +115,35 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
 // ================================================================================================
 // Host side: C ABI
 // ================================================================================================
+// The launch record: the distinct kernel builds the last train call of a population launched, each with its template arguments and a
+// launch count (mfas_population_launch_record).  An entry is made where the launch is made, from the Build the launch takes its function
+// pointer from (the kernel tables below), so the record cannot name another instantiation than the one that ran.
+struct LaunchRecord {
+    struct Entry { const void* fn; const char* family; int narg; int arg[5]; int64_t n; };
+    std::vector<Entry> entries;     // a handful: one per build, found by its function pointer
+    void clear() { entries.clear(); }
+    void count(const void* fn, const char* family, int narg, const int* arg) {
+        for (Entry& e : entries) if (e.fn == fn) { ++e.n; return; }
+        Entry e{fn, family, narg, {0, 0, 0, 0, 0}, 1};
+        for (int i = 0; i < narg && i < 5; ++i) e.arg[i] = arg[i];
+        entries.push_back(e);
+    }
+    // "k_step<1,1,4,0,1>:7 k_chain<1,0>:8 ...", sorted by name
+    std::string describe() const {
+        std::vector<std::string> items;
+        for (const Entry& e : entries) {
+            std::string s = e.family;
+            for (int i = 0; i < e.narg; ++i) s += (i ? "," : "<") + std::to_string(e.arg[i]);
+            if (e.narg) s += ">";
+            items.push_back(s + ":" + std::to_string(e.n));
+        }
+        std::sort(items.begin(), items.end());
+        std::string out;
+        for (const std::string& s : items) out += (out.empty() ? "" : " ") + s;
+        return out;
+    }
+};
+
 struct mfas_population {
     mfas_hyper hp;
     Tuning tune;                    // the environment switches as they stood when the population was created
@@ -142,7 +171,8 @@ struct mfas_population {
     std::vector<hipEvent_t> ev;     // pairs
     int64_t prof_launches = 0;
     double prof_ms = 0.0, bytes_per_launch = 0.0, prof_bytes = 0.0;
-    double best_threshold = 0.0;    // snapshot_best: a dev metric must exceed this to count (init_f1, mmimdb.py:18; 0 for NTU)
+    LaunchRecord launched;          // the builds the last train call launched (cleared when a call has passed its checks)
+    double best_threshold = 0.0;   // snapshot_best: a dev metric must exceed this to count (init_f1, mmimdb.py:18; 0 for NTU)
     // Progress record (mfas_population_train_from): what train_ntu_track_acc keeps on its stack for one call (best_acc,
     // train_searchable/ntu.py:18,82-83) and where in its schedule every candidate stands, kept between calls.  Per candidate: a moved
     // candidate (mfas_population_move) brings its own.
@@ -214,57 +244,85 @@ static hipError_t set_lds(KT kernel, size_t bytes) {
 // Kernel tables: every instantiation of a family is named HERE and nowhere else.  create sets the dynamic-LDS limit through these
 // functions (set_lds_all) and train / single_batch launch through them, so a build cannot be launched without its limit having been set.
 // A parameter combination that is not built gives nullptr.
+// A table row is a Build: the instantiation's pointer AND its template arguments, both written by ONE function template per family
+// (*_of below) from the same template parameters — the name the launch record keeps is the name of the instantiation that is launched,
+// whatever the row's condition says.
 // ------------------------------------------------------------------------------------------------
 typedef void (*StepKernel)(const StepArgs);
 typedef void (*ChainKernel)(const ChainArgs);
 typedef void (*PresidentKernel)(const PersistArgs, const int);
 
+template <typename KT>
+struct Build { KT fn = nullptr; const char* family = ""; int narg = 0; int arg[5] = {0, 0, 0, 0, 0}; };
+typedef Build<StepKernel> StepBuild;
+typedef Build<ChainKernel> ChainBuild;
+typedef Build<PresidentKernel> PresidentBuild;
+
+template <int MB, bool NT, int NS> static StepBuild same_of() { return {k_step_same<MB, NT, NS>, "k_step_same", 3, {MB, NT, NS, 0, 0}}; }
+template <int MB, bool NT, int WPE, bool LEAN, int NS> static StepBuild step_of() { return {k_step<MB, NT, WPE, LEAN, NS>, "k_step", 5, {MB, NT, WPE, LEAN, NS}}; }
+template <int MB, bool LEAN> static ChainBuild chain_of() { return {k_chain<MB, LEAN>, "k_chain", 2, {MB, LEAN, 0, 0, 0}}; }
+template <bool NT> static StepBuild wide_sweep_of() { return {k_sweep_wide<NT>, "k_sweep_wide", 1, {NT, 0, 0, 0, 0}}; }
+template <int MB, int NTR, bool X16, int NU, int PLAIN> static PresidentBuild president_of() { return {k_president<MB, NTR, X16, NU, PLAIN>, "k_president", 5, {MB, NTR, X16, NU, PLAIN}}; }
+
 // (the order below is the order the builds come out in the code object: tools/kernel_resources.py lists them that way)
-static StepKernel same_kernel(int MB, bool nt, int ns) {
-#define K_(M, S) if (MB == M && ns == S) return !nt ? k_step_same<M, false, S> : k_step_same<M, true, S>
+static StepBuild same_build(int MB, bool nt, int ns) {
+#define K_(M, S) if (MB == M && ns == S) return !nt ? same_of<M, false, S>() : same_of<M, true, S>()
     K_(1, 1); K_(2, 1); K_(1, 4);
 #undef K_
-    return nullptr;
+    return StepBuild();
 }
+static StepKernel same_kernel(int MB, bool nt, int ns) { return same_build(MB, nt, ns).fn; }
 
-static StepKernel step_kernel(int MB, bool nt, int wpe, bool lean, int ns) {
-#define K_(M, W, F, S) if (MB == M && wpe == W && lean == F && ns == S) return !nt ? k_step<M, false, W, F, S> : k_step<M, true, W, F, S>
+static StepBuild step_build(int MB, bool nt, int wpe, bool lean, int ns) {
+#define K_(M, W, F, S) if (MB == M && wpe == W && lean == F && ns == S) return !nt ? step_of<M, false, W, F, S>() : step_of<M, true, W, F, S>()
     K_(1, 4, false, 4);
     K_(1, 4, false, 1); K_(2, 2, false, 1); K_(2, 4, false, 1); K_(4, 2, false, 1);
     K_(1, 4, true, 1); K_(2, 2, true, 1); K_(2, 4, true, 1);
 #undef K_
-    return nullptr;
+    return StepBuild();
 }
+static StepKernel step_kernel(int MB, bool nt, int wpe, bool lean, int ns) { return step_build(MB, nt, wpe, lean, ns).fn; }
 
-static ChainKernel chain_kernel(int MB, bool lean) {
-    if (!lean && MB == 1) return k_chain<1, false>;
-    if (!lean && MB == 2) return k_chain<2, false>;
-    if (!lean && MB == 4) return k_chain<4, false>;
-    if (lean && MB == 1) return k_chain<1, true>;
-    if (lean && MB == 2) return k_chain<2, true>;
-    return nullptr;
+static ChainBuild chain_build(int MB, bool lean) {
+    if (!lean && MB == 1) return chain_of<1, false>();
+    if (!lean && MB == 2) return chain_of<2, false>();
+    if (!lean && MB == 4) return chain_of<4, false>();
+    if (lean && MB == 1) return chain_of<1, true>();
+    if (lean && MB == 2) return chain_of<2, true>();
+    return ChainBuild();
 }
+static ChainKernel chain_kernel(int MB, bool lean) { return chain_build(MB, lean).fn; }
 
 // the wide path (wide.hip.h): one chain build, the sweep with cached / nontemporal W/m/v streaming
-static ChainKernel wide_chain_kernel() { return k_chain_wide; }
-static StepKernel wide_sweep_kernel(bool nt) { return !nt ? k_sweep_wide<false> : k_sweep_wide<true>; }
+static ChainBuild wide_chain_build() { return {k_chain_wide, "k_chain_wide", 0, {0, 0, 0, 0, 0}}; }
+static ChainKernel wide_chain_kernel() { return wide_chain_build().fn; }
+static StepBuild wide_sweep_build(bool nt) { return !nt ? wide_sweep_of<false>() : wide_sweep_of<true>(); }
+static StepKernel wide_sweep_kernel(bool nt) { return wide_sweep_build(nt).fn; }
 
 // one instantiation per unit form: f32 staging (one or two units per workgroup), 16-bit staging (the same, or one WIDE unit of up to
 // 1024 columns); plain: the chain compiled for the search default (1), for `--batchnorm` alone (2), or the general one (0)
-static PresidentKernel president_kernel(int MB, bool x16, bool wide, int nu, int plain) {
+static PresidentBuild president_build(int MB, bool x16, bool wide, int nu, int plain) {
 #define K_(M, P) if (MB == M && plain == P) { \
-        if (!x16) return nu != 2 ? k_president<M, PERSIST_NTR, false, 1, P> : k_president<M, PERSIST_NTR, false, 2, P>; \
-        if (wide) return k_president<M, PERSIST_NTR16, true, 1, P>; \
-        return nu != 2 ? k_president<M, PERSIST_NTR, true, 1, P> : k_president<M, PERSIST_NTR, true, 2, P>; }
+        if (!x16) return nu != 2 ? president_of<M, PERSIST_NTR, false, 1, P>() : president_of<M, PERSIST_NTR, false, 2, P>(); \
+        if (wide) return president_of<M, PERSIST_NTR16, true, 1, P>(); \
+        return nu != 2 ? president_of<M, PERSIST_NTR, true, 1, P>() : president_of<M, PERSIST_NTR, true, 2, P>(); }
     K_(1, 0) K_(2, 0) K_(1, 1) K_(2, 1) K_(1, 2) K_(2, 2)
 #undef K_
-    return nullptr;
+    return PresidentBuild();
 }
+static PresidentKernel president_kernel(int MB, bool x16, bool wide, int nu, int plain) { return president_build(MB, x16, wide, nu, plain).fn; }
 
 template <typename... A>
 static void launch(void (*kernel)(A...), unsigned grid, size_t lds, hipStream_t stream, A... args) {
     void* argv[] = {const_cast<void*>(static_cast<const void*>(&args))...};
     (void)hipLaunchKernel(reinterpret_cast<const void*>(kernel), dim3(grid), dim3(STEP_THREADS), argv, lds, stream);    // (errors: hipGetLastError)
+}
+
+// a launch of a train call: counted in the population's launch record, then made
+template <typename... A>
+static void launch_build(mfas_population* p, const Build<void (*)(A...)>& b, unsigned grid, size_t lds, hipStream_t stream, A... args) {
+    if (b.fn) p->launched.count(reinterpret_cast<const void*>(b.fn), b.family, b.narg, b.arg);
+    launch(b.fn, grid, lds, stream, args...);
 }
 
 // the dynamic-LDS limit of every build a population with this plan may launch
@@ -657,6 +715,13 @@ extern "C" int mfas_population_schedule(const mfas_population* p, int32_t info[8
     const LayoutPlan& pl = p->plan;
     info[0] = pl.persist ? 1 : 0; info[1] = pl.nres; info[2] = pl.nres_wg; info[3] = pl.res_nu;
     info[4] = pl.res_chain ? 1 : 0; info[5] = (pl.lean_chain ? 1 : 0) | (pl.wide ? 2 : 0) | (std::max(1, pl.chain_split) << 8); info[6] = pl.same_group ? -1 : (int32_t)pl.groups.size(); info[7] = p->K;
+    return MFAS_OK;
+}
+
+// "family<template arguments>:launches ..." of the builds the last train call launched, sorted by name
+extern "C" int mfas_population_launch_record(const mfas_population* p, char* buf, int32_t cap) {
+    if (!p || !buf || cap <= 0) return fail(MFAS_EINVAL, "null");
+    snprintf(buf, (size_t)cap, "%s", p->launched.describe().c_str());
     return MFAS_OK;
 }
 

@@ -222,6 +222,7 @@ static int persist_fallback(mfas_population* p) {
     std::swap(q->d_scal, p->d_scal); std::swap(q->scal_cap, p->scal_cap);
     q->ev.swap(p->ev); q->profiling = p->profiling; q->prof_every = p->prof_every;
     q->best_threshold = p->best_threshold; q->prog = p->prog; q->fell_back = 1;
+    q->launched = p->launched;      // (the call's launch record goes on: the resident launches that were made, then the launch-per-phase ones)
     std::swap(*p, *q);
     mfas_population_destroy(q);      // the resident layout
     return MFAS_OK;

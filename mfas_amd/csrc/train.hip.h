@@ -105,16 +105,16 @@ struct ProfBracket {
 
 // The build that carries a launch with a sweep in it, over the plan and the record.  nch: candidates of its chain (0: none); same:
 // chain(g, t) and sweep(g, t) in ONE launch behind per-cell flags; split: the chain blocks are chain_split parts
-static StepKernel pick_step_kernel(const LayoutPlan& pl, const Launch& L, unsigned nch, bool same, bool split) {
+static StepBuild pick_step_kernel(const LayoutPlan& pl, const Launch& L, unsigned nch, bool same, bool split) {
     const int MB = pl.g.MB;
-    if (pl.wide) return wide_sweep_kernel(pl.nontemporal);      // launch per phase only: the sweep of the one group, after its chain's launch
-    if (same) return same_kernel(MB, pl.nontemporal, split ? pl.chain_split : 1);
-    if (split) return step_kernel(MB, pl.nontemporal, 4, false, pl.chain_split);
+    if (pl.wide) return wide_sweep_build(pl.nontemporal);      // launch per phase only: the sweep of the one group, after its chain's launch
+    if (same) return same_build(MB, pl.nontemporal, split ? pl.chain_split : 1);
+    if (split) return step_build(MB, pl.nontemporal, 4, false, pl.chain_split);
     // MB == 2: the two-workgroups-per-CU build unless a co-scheduled chain would bound the launch (see SweepU)
     // (lean chain: the 128-VGPR build spills 8 registers of the element-parallel chain to scratch and is still the faster
     //  one — R=16, B=20, 50 / 128 / 512 candidates: 47.2 / 99.2 / 418 us per step against 50.5 / 117.4 / 447 for the 2-workgroup build)
     const bool occ = nch == 0 || pl.groups[L.sweep_g].alg_state > pl.occ_bytes;
-    return step_kernel(MB, pl.nontemporal, MB == 1 || (MB == 2 && (occ || pl.lean_chain)) ? 4 : 2, pl.lean_chain, 1);
+    return step_build(MB, pl.nontemporal, MB == 1 || (MB == 2 && (occ || pl.lean_chain)) ? 4 : 2, pl.lean_chain, 1);
 }
 
 // one record of the launch list -> one launch of epoch ep: the step-dependent arguments (positions and valid rows, step scalars, flag
@@ -164,7 +164,7 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
     }
     st.nchain = (int)nch;
     if (nsw == 0) {   // chain only: the latency-tuned standalone kernel (wide populations: theirs)
-        launch(pl.wide ? wide_chain_kernel() : chain_kernel(pl.g.MB, pl.lean_chain), nch, pl.lds_chain, p->stream, st.ca);
+        launch_build(p, pl.wide ? wide_chain_build() : chain_build(pl.g.MB, pl.lean_chain), nch, pl.lds_chain, p->stream, st.ca);
         return;
     }
     // algorithmic HBM bytes of this group's update+forward sweep: 24 B/param + the batch's taps + labels
@@ -180,7 +180,7 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
         st.sa.flag_target = st.ca.flag_target = (split ? (uint32_t)pl.chain_split : 1u) * ((uint32_t)st.ca.gstep + 1u);
         st.sa.flag_status = p->d_status;
     }
-    launch(pick_step_kernel(pl, L, nch, same, split), (unsigned)st.nchain + st.ga.nblocks + nsw, split ? pl.lds_split : pl.lds_step, p->stream, st);
+    launch_build(p, pick_step_kernel(pl, L, nch, same, split), (unsigned)st.nchain + st.ga.nblocks + nsw, split ? pl.lds_split : pl.lds_step, p->stream, st);
     if (same) { st.sa.cellflag = nullptr; st.ca.cellflag = nullptr; }
 }
 
@@ -216,7 +216,7 @@ static hipError_t persist_epoch_once(TrainCall& c, int ep, int64_t T) {
         // (round 6: and `--batchnorm` alone, main_searchable_ntu.py:48 of the reference, the chain compiled for exactly THAT — PLAIN = 2)
         const bool simple = !g.alphas && !g.multitask && g.loss_mode == 0 && !p->tune.no_plain_chain;
         const bool x16 = c.train->dtype != MFAS_DT_F32;
-        launch(president_kernel(g.MB, x16, x16 && pl.res_wide, pl.res_nu, simple ? (g.bn ? 2 : 1) : 0), grid, pl.lds_president, p->stream, pa, lw);
+        launch_build(p, president_build(g.MB, x16, x16 && pl.res_wide, pl.res_nu, simple ? (g.bn ? 2 : 1) : 0), grid, pl.lds_president, p->stream, pa, lw);
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -478,6 +478,7 @@ static int train_impl(mfas_population* p, const mfas_table* train, const mfas_ta
     c.p = p; c.train = train; c.dev = dev; c.order = order; c.step_scalars = step_scalars; c.epochs = epochs; c.max_steps = max_steps;
     c.snapshot_best = snapshot_best != 0; c.first = first; c.last = last; c.segment = segment;
     if (int rc = train_check(c, stats)) return rc;
+    p->launched.clear();      // the launch record is the record of this call (launch_record, persist_epoch_once)
     RangeGuard call_range("mfas_population_train K=" + std::to_string(p->K) + " R=" + std::to_string(p->plan.g.R) + " B=" + std::to_string(c.B) +
                           " E=" + std::to_string(epochs) + (p->plan.persist ? " resident" : " launch-per-phase"));
     if (int rc = train_begin(c)) return rc;

@@ -526,6 +526,13 @@ class Population:
         d["lean_chain"] &= 1
         return d
 
+    def launch_record(self) -> Dict[str, int]:
+        """{build name: launches} of the kernel builds the last train() call launched (mfas_population_launch_record), e.g.
+        {"k_step<1,1,4,0,1>": 7, "k_chain<1,0>": 8}: recorded by the library where it makes the launches."""
+        buf = C.create_string_buffer(4096)
+        _lib.check(self.lib.mfas_population_launch_record(self._h, buf, 4096))
+        return {name: int(n) for name, n in (item.rsplit(":", 1) for item in buf.value.decode().split())}
+
     def sweep_profile(self):
         n, ms, by = C.c_int64(0), C.c_double(0), C.c_double(0)
         _lib.check(self.lib.mfas_population_sweep_profile(self._h, C.byref(n), C.byref(ms), C.byref(by)))

@@ -102,15 +102,18 @@ def train_rows(B, full=1):
     return full * B + ragged_rows(B)
 
 
-def engine_states(pop, tab, p0s, etas, order_t, steps=(1, 2, 3)):
+def engine_states(pop, tab, p0s, etas, order_t, steps=(1, 2, 3), after_call=None):
     """{j: state of every candidate} and {j: statistics} of the j-step calls, j in {0} | steps | {s - 1 for s in steps}: the same
-    initial parameters before each call."""
+    initial parameters before each call.  after_call(j, pop): called right after the j-step call (tests/test_gpu_step_builds_ref64.py
+    reads the launch record there)."""
     S, ST = {}, {}
     for j in sorted({0} | set(steps) | {s - 1 for s in steps}):
         for k, p0 in enumerate(p0s):
             pop.set_state_dict(k, p0)
         stats, status = pop.train(tab, None, EPOCHS, etas, order=order_t, max_steps=j)
         assert not status.any(), (j, status)
+        if after_call is not None:
+            after_call(j, pop)
         S[j] = [{"w": state_np(pop, k, 0), "m": state_np(pop, k, 1), "v": state_np(pop, k, 2)} for k in range(len(p0s))]
         ST[j] = stats.copy()
     return S, ST

@@ -328,9 +328,11 @@ def stale_taps(batch, stale):
     return {k: (stale[k][:n] if k[0] in "sv" and k[1:].isdigit() else v) for k, v in batch.items()}
 
 
-def oracle_steps(conf, hp, p0, t, order, etas, seed, steps, taus, tag, mut="", wrong=None, batch_sum_term=False):
+def oracle_steps(conf, hp, p0, t, order, etas, seed, steps, taus, tag, mut="", wrong=None, batch_sum_term=False, post=None):
     """The float32 oracle through steps 1..steps[-1] of one candidate (table t, sample order [EPOCHS][N], dropout seed), every
-    step of `steps` checked against ref64 from the oracle's own state before it: worst ratio per quantity."""
+    step of `steps` checked against ref64 from the oracle's own state before it: worst ratio per quantity.
+    post(j, prev, new, again) -> state: what step j leaves, changed before it is checked and carried on (again(state): the same
+    step run from another state); tests/test_step_builds_cpu.py drops and repeats a tile's stores with it."""
     N = order.shape[1]
     pw = G.pos_weight(hp) if hp.loss_mode == 1 else None
     keys = O.trainable_keys(conf, hp)
@@ -360,6 +362,8 @@ def oracle_steps(conf, hp, p0, t, order, etas, seed, steps, taus, tag, mut="", w
             idx = order[ep][(bi % 2) * hp.B:(bi % 2) * hp.B + n]
             seen = {k: v[idx] for k, v in t.items()}
         new, loss, count = oracle_step32(hist[-1], conf, hp, seen, seed, j - 1, eta_j, t_j, pw, m, stale)
+        if post is not None:
+            new = post(j, hist[-1], new, lambda st: oracle_step32(st, conf, hp, seen, seed, j - 1, eta_j, t_j, pw, m, stale)[0])
         if j in steps:
             exp = R64.train_step64(hist[-1], conf, hp, batch, seed, j - 1, etas[j - 1], j, G.TAU_LOGITS, GT.TAU_V, observed=new, pos_weight=pw,
                                      batch_sum_term=batch_sum_term)
