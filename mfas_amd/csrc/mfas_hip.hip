@@ -18,8 +18,9 @@
 // (tile_run, sweep_body, sweep_tap_body), chain.hip.h (chain_body, chain_lean, softmax / BCE rows), wide.hip.h (k_chain_wide / k_sweep_wide:
 // the batch walked in tiles), eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe); host only: plan.hip.h (the switches,
 // validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated), launches.hip.h (the
-// launches of an epoch as data), state.hip.h (state in and out, the candidate carry, move, the fallback), train.hip.h (the train call).  Here:
-// k_step / k_chain, the kernel tables (one function per family: the only place an instantiation is named), create / destroy, the C ABI.
+// launches of an epoch as data), builds.hip.h (which build a launch takes, as data: the choice functions, the builds a plan can launch, the
+// tables' row lists), state.hip.h (state in and out, the candidate carry, move, the fallback), train.hip.h (the train call).  Here:
+// k_step / k_chain, the kernel tables (key -> instantiation: the only place one is named), create / destroy, the C ABI.
 // Dev evaluation is row-parallel (k_eval).  Weights live in a 16x16 tile-major layout that is exactly the
 // MFMA 16x16x4 f32 operand layout, so every W/m/v access is one coalesced 16 B/lane load.
 //
@@ -110,6 +111,7 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
 #include "eval.hip.h"
 #include "pack.hip.h"
 
+#include "builds.hip.h"
 #include "plan.hip.h"
 
 // ================================================================================================
@@ -119,24 +121,17 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
 // launch count (mfas_population_launch_record).  An entry is made where the launch is made, from the Build the launch takes its function
 // pointer from (the kernel tables below), so the record cannot name another instantiation than the one that ran.
 struct LaunchRecord {
-    struct Entry { const void* fn; const char* family; int narg; int arg[5]; int64_t n; };
+    struct Entry { BuildKey key; const void* fn; int64_t n; };
     std::vector<Entry> entries;     // a handful: one per build, found by its function pointer
     void clear() { entries.clear(); }
-    void count(const void* fn, const char* family, int narg, const int* arg) {
+    void count(const BuildKey& key, const void* fn) {
         for (Entry& e : entries) if (e.fn == fn) { ++e.n; return; }
-        Entry e{fn, family, narg, {0, 0, 0, 0, 0}, 1};
-        for (int i = 0; i < narg && i < 5; ++i) e.arg[i] = arg[i];
-        entries.push_back(e);
+        entries.push_back(Entry{key, fn, 1});
     }
     // "k_step<1,1,4,0,1>:7 k_chain<1,0>:8 ...", sorted by name
     std::string describe() const {
         std::vector<std::string> items;
-        for (const Entry& e : entries) {
-            std::string s = e.family;
-            for (int i = 0; i < e.narg; ++i) s += (i ? "," : "<") + std::to_string(e.arg[i]);
-            if (e.narg) s += ">";
-            items.push_back(s + ":" + std::to_string(e.n));
-        }
+        for (const Entry& e : entries) items.push_back(e.key.name() + ":" + std::to_string(e.n));
         std::sort(items.begin(), items.end());
         std::string out;
         for (const std::string& s : items) out += (out.empty() ? "" : " ") + s;
@@ -241,76 +236,74 @@ static hipError_t set_lds(KT kernel, size_t bytes) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Kernel tables: every instantiation of a family is named HERE and nowhere else.  create sets the dynamic-LDS limit through these
-// functions (set_lds_all) and train / single_batch launch through them, so a build cannot be launched without its limit having been set.
-// A parameter combination that is not built gives nullptr.
-// A table row is a Build: the instantiation's pointer AND its template arguments, both written by ONE function template per family
-// (*_of below) from the same template parameters — the name the launch record keeps is the name of the instantiation that is launched,
-// whatever the row's condition says.
+// Kernel tables: every instantiation of a family is named HERE and nowhere else, one row per entry of the family's row list in
+// builds.hip.h.  A row is a Build: the instantiation's pointer AND its key, both written by ONE function template per family (*_of below)
+// from the same template parameters — the name the launch record keeps is the name of the instantiation that is launched.  A launch
+// chooses a key (builds.hip.h) and looks its row up; create sets the dynamic-LDS limit of the rows of plan_keys (set_lds_all), the keys a
+// population with that plan can choose.  A key that is not built gives nullptr.
 // ------------------------------------------------------------------------------------------------
+static_assert(BUILDS_NTR == PERSIST_NTR && BUILDS_NTR16 == PERSIST_NTR16 && BUILDS_DT_BF16 == MFAS_DT_BF16, "builds.hip.h restates these");
 typedef void (*StepKernel)(const StepArgs);
 typedef void (*ChainKernel)(const ChainArgs);
 typedef void (*PresidentKernel)(const PersistArgs, const int);
+typedef hipError_t (*EvalLaunch)(mfas_population*, const EvalArgs&, int, hipStream_t);      // (launch_eval_t: the dev pass sets its LDS limit per launch)
 
 template <typename KT>
-struct Build { KT fn = nullptr; const char* family = ""; int narg = 0; int arg[5] = {0, 0, 0, 0, 0}; };
+struct Build { BuildKey key; KT fn = nullptr; };
 typedef Build<StepKernel> StepBuild;
 typedef Build<ChainKernel> ChainBuild;
 typedef Build<PresidentKernel> PresidentBuild;
+typedef Build<EvalLaunch> EvalBuild;
 
-template <int MB, bool NT, int NS> static StepBuild same_of() { return {k_step_same<MB, NT, NS>, "k_step_same", 3, {MB, NT, NS, 0, 0}}; }
-template <int MB, bool NT, int WPE, bool LEAN, int NS> static StepBuild step_of() { return {k_step<MB, NT, WPE, LEAN, NS>, "k_step", 5, {MB, NT, WPE, LEAN, NS}}; }
-template <int MB, bool LEAN> static ChainBuild chain_of() { return {k_chain<MB, LEAN>, "k_chain", 2, {MB, LEAN, 0, 0, 0}}; }
-template <bool NT> static StepBuild wide_sweep_of() { return {k_sweep_wide<NT>, "k_sweep_wide", 1, {NT, 0, 0, 0, 0}}; }
-template <int MB, int NTR, bool X16, int NU, int PLAIN> static PresidentBuild president_of() { return {k_president<MB, NTR, X16, NU, PLAIN>, "k_president", 5, {MB, NTR, X16, NU, PLAIN}}; }
+template <int MBE, int NRBW, int MSP, bool XB, bool B3>
+static hipError_t launch_eval_t(mfas_population* p, const EvalArgs& a, int ncand, hipStream_t st);
 
-// (the order below is the order the builds come out in the code object: tools/kernel_resources.py lists them that way)
-static StepBuild same_build(int MB, bool nt, int ns) {
-#define K_(M, S) if (MB == M && ns == S) return !nt ? same_of<M, false, S>() : same_of<M, true, S>()
-    K_(1, 1); K_(2, 1); K_(1, 4);
-#undef K_
-    return StepBuild();
+template <int MB, bool NT, int WPE, bool LEAN, int NS> static StepBuild step_of() { return {step_key_of(MB, NT, WPE, LEAN, NS), k_step<MB, NT, WPE, LEAN, NS>}; }
+template <int MB, bool NT, int NS> static StepBuild same_of() { return {same_key_of(MB, NT, NS), k_step_same<MB, NT, NS>}; }
+template <bool NT> static StepBuild wide_sweep_of() { return {sweep_wide_key_of(NT), k_sweep_wide<NT>}; }
+template <int MB, bool LEAN> static ChainBuild chain_of() { return {chain_key_of(MB, LEAN), k_chain<MB, LEAN>}; }
+template <int MB, int NTR, bool X16, int NU, int PLAIN> static PresidentBuild president_of() { return {president_key_of(MB, NTR, X16, NU, PLAIN), k_president<MB, NTR, X16, NU, PLAIN>}; }
+template <int MBE, int NRBW, int MSP, bool XB, bool B3> static EvalBuild eval_of() { return {eval_key_of(MBE, NRBW, MSP, XB, B3), launch_eval_t<MBE, NRBW, MSP, XB, B3>}; }
+
+template <typename KT, size_t N>
+static Build<KT> find_build(const Build<KT> (&rows)[N], const BuildKey& key) {
+    for (const Build<KT>& r : rows) if (r.key == key) return r;
+    return Build<KT>();
 }
-static StepKernel same_kernel(int MB, bool nt, int ns) { return same_build(MB, nt, ns).fn; }
 
-static StepBuild step_build(int MB, bool nt, int wpe, bool lean, int ns) {
-#define K_(M, W, F, S) if (MB == M && wpe == W && lean == F && ns == S) return !nt ? step_of<M, false, W, F, S>() : step_of<M, true, W, F, S>()
-    K_(1, 4, false, 4);
-    K_(1, 4, false, 1); K_(2, 2, false, 1); K_(2, 4, false, 1); K_(4, 2, false, 1);
-    K_(1, 4, true, 1); K_(2, 2, true, 1); K_(2, 4, true, 1);
-#undef K_
-    return StepBuild();
+// the launches with a sweep in them: k_step, k_step_same, k_sweep_wide (wide.hip.h)
+static StepBuild step_build(const BuildKey& key) {
+#define STEP_(...) step_of<__VA_ARGS__>(),
+#define SAME_(...) same_of<__VA_ARGS__>(),
+#define WIDE_(...) wide_sweep_of<__VA_ARGS__>(),
+    static const StepBuild rows[] = {BUILDS_SAME_ROWS(SAME_) BUILDS_STEP_ROWS(STEP_) BUILDS_SWEEP_WIDE_ROWS(WIDE_)};
+#undef STEP_
+#undef SAME_
+#undef WIDE_
+    return find_build(rows, key);
 }
-static StepKernel step_kernel(int MB, bool nt, int wpe, bool lean, int ns) { return step_build(MB, nt, wpe, lean, ns).fn; }
 
-static ChainBuild chain_build(int MB, bool lean) {
-    if (!lean && MB == 1) return chain_of<1, false>();
-    if (!lean && MB == 2) return chain_of<2, false>();
-    if (!lean && MB == 4) return chain_of<4, false>();
-    if (lean && MB == 1) return chain_of<1, true>();
-    if (lean && MB == 2) return chain_of<2, true>();
-    return ChainBuild();
+// the standalone chain, and the wide path's
+static ChainBuild chain_build(const BuildKey& key) {
+#define CHAIN_(...) chain_of<__VA_ARGS__>(),
+    static const ChainBuild rows[] = {BUILDS_CHAIN_ROWS(CHAIN_) {chain_wide_key_of(), k_chain_wide}};
+#undef CHAIN_
+    return find_build(rows, key);
 }
-static ChainKernel chain_kernel(int MB, bool lean) { return chain_build(MB, lean).fn; }
 
-// the wide path (wide.hip.h): one chain build, the sweep with cached / nontemporal W/m/v streaming
-static ChainBuild wide_chain_build() { return {k_chain_wide, "k_chain_wide", 0, {0, 0, 0, 0, 0}}; }
-static ChainKernel wide_chain_kernel() { return wide_chain_build().fn; }
-static StepBuild wide_sweep_build(bool nt) { return !nt ? wide_sweep_of<false>() : wide_sweep_of<true>(); }
-static StepKernel wide_sweep_kernel(bool nt) { return wide_sweep_build(nt).fn; }
-
-// one instantiation per unit form: f32 staging (one or two units per workgroup), 16-bit staging (the same, or one WIDE unit of up to
-// 1024 columns); plain: the chain compiled for the search default (1), for `--batchnorm` alone (2), or the general one (0)
-static PresidentBuild president_build(int MB, bool x16, bool wide, int nu, int plain) {
-#define K_(M, P) if (MB == M && plain == P) { \
-        if (!x16) return nu != 2 ? president_of<M, PERSIST_NTR, false, 1, P>() : president_of<M, PERSIST_NTR, false, 2, P>(); \
-        if (wide) return president_of<M, PERSIST_NTR16, true, 1, P>(); \
-        return nu != 2 ? president_of<M, PERSIST_NTR, true, 1, P>() : president_of<M, PERSIST_NTR, true, 2, P>(); }
-    K_(1, 0) K_(2, 0) K_(1, 1) K_(2, 1) K_(1, 2) K_(2, 2)
-#undef K_
-    return PresidentBuild();
+static PresidentBuild president_build(const BuildKey& key) {
+#define PRES_(...) president_of<__VA_ARGS__>(),
+    static const PresidentBuild rows[] = {BUILDS_PRESIDENT_ROWS(PRES_)};
+#undef PRES_
+    return find_build(rows, key);
 }
-static PresidentKernel president_kernel(int MB, bool x16, bool wide, int nu, int plain) { return president_build(MB, x16, wide, nu, plain).fn; }
+
+static EvalBuild eval_build(const BuildKey& key) {
+#define EVAL_(...) eval_of<__VA_ARGS__>(),
+    static const EvalBuild rows[] = {BUILDS_EVAL_ROWS(EVAL_)};
+#undef EVAL_
+    return find_build(rows, key);
+}
 
 template <typename... A>
 static void launch(void (*kernel)(A...), unsigned grid, size_t lds, hipStream_t stream, A... args) {
@@ -321,30 +314,22 @@ static void launch(void (*kernel)(A...), unsigned grid, size_t lds, hipStream_t 
 // a launch of a train call: counted in the population's launch record, then made
 template <typename... A>
 static void launch_build(mfas_population* p, const Build<void (*)(A...)>& b, unsigned grid, size_t lds, hipStream_t stream, A... args) {
-    if (b.fn) p->launched.count(reinterpret_cast<const void*>(b.fn), b.family, b.narg, b.arg);
+    if (b.fn) p->launched.count(b.key, reinterpret_cast<const void*>(b.fn));
     launch(b.fn, grid, lds, stream, args...);
 }
 
-// the dynamic-LDS limit of every build a population with this plan may launch
+// the dynamic-LDS limit of every build a population with this plan can launch (the dev pass sets its own per launch: launch_eval_t)
 static hipError_t set_lds_all(const LayoutPlan& pl) {
     hipError_t e = hipSuccess;
     auto set = [&e](auto kernel, size_t bytes) { if (kernel && e == hipSuccess) e = set_lds(kernel, bytes); };
-    if (pl.wide) {
-        set(wide_chain_kernel(), pl.lds_chain);
-        for (int b = 0; b < 2; ++b) set(wide_sweep_kernel(b), pl.lds_step);
-        return e;
-    }
-    for (int MB : {1, 2, 4})
-        for (int b = 0; b < 2; ++b) {      // b: nontemporal (k_step*), lean (k_chain), 16-bit staging (k_president)
-            for (int wpe : {2, 4}) { set(step_kernel(MB, b, wpe, false, 1), pl.lds_step); set(step_kernel(MB, b, wpe, true, 1), pl.lds_step); }
-            if (pl.same_group) set(same_kernel(MB, b, 1), pl.lds_step);
-            if (pl.chain_split) { set(same_kernel(MB, b, 4), pl.lds_split); set(step_kernel(MB, b, 4, false, 4), pl.lds_split); }
-            set(chain_kernel(MB, b), pl.lds_chain);
-            if (pl.persist)
-                for (int plain = 0; plain < 3; ++plain) {
-                    set(president_kernel(MB, b, false, 1, plain), pl.lds_president); set(president_kernel(MB, b, false, 2, plain), pl.lds_president);
-                    if (b) set(president_kernel(MB, true, true, 1, plain), pl.lds_president);
-                }
+    for (const BuildKey& key : plan_keys(plan_facts(pl)))
+        switch (key.family) {
+            case F_STEP: set(step_build(key).fn, key.arg[4] > 1 ? pl.lds_split : pl.lds_step); break;
+            case F_STEP_SAME: set(step_build(key).fn, key.arg[2] > 1 ? pl.lds_split : pl.lds_step); break;
+            case F_SWEEP_WIDE: set(step_build(key).fn, pl.lds_step); break;
+            case F_CHAIN: case F_CHAIN_WIDE: set(chain_build(key).fn, pl.lds_chain); break;
+            case F_PRESIDENT: set(president_build(key).fn, pl.lds_president); break;
+            default: break;
         }
     return e;
 }
@@ -491,7 +476,7 @@ static int check_table(const mfas_population* p, const mfas_table* t, bool need_
     return MFAS_OK;
 }
 
-template <int MBE, int NRBW, int MSP = 0, bool XB = false, bool B3 = false>
+template <int MBE, int NRBW, int MSP, bool XB, bool B3>
 static hipError_t launch_eval_t(mfas_population* p, const EvalArgs& a, int ncand, hipStream_t st) {
     const int ME = MBE * 16;
     // (16-bit row tile: half the width, more workgroups per CU)
@@ -509,25 +494,9 @@ static hipError_t launch_eval_t(mfas_population* p, const EvalArgs& a, int ncand
 }
 
 static hipError_t launch_eval(mfas_population* p, const EvalArgs& a, int ncand, hipStream_t st) {
-    // one or two row blocks (R <= 32): the m-blocks of a row tile are split over the four waves (eval.hip.h)
-    // (bf16 tables: the rows stay 16-bit in LDS)
-    const bool xb = a.tab.dtype == MFAS_DT_BF16 && !p->tune.eval_no_x16;
-#define EV_SPLIT(M, S) if (p->plan.mbe == M && p->plan.nrbw == 1 && p->plan.g.nrb == S && !p->tune.eval_no_msplit) \
-        return xb ? launch_eval_t<M, 1, S, true>(p, a, ncand, st) : launch_eval_t<M, 1, S, false>(p, a, ncand, st);
-    EV_SPLIT(4, 1) EV_SPLIT(4, 2) EV_SPLIT(2, 1) EV_SPLIT(2, 2) EV_SPLIT(1, 1) EV_SPLIT(1, 2)
-#undef EV_SPLIT
-    // two row blocks per wave (R = 72 .. 128), bf16 tables: exact bf16 x 3 feature products on the bf16 matrix pipe
-    if (a.tab.dtype == MFAS_DT_BF16 && p->plan.nrbw == 2 && !p->tune.eval_no_b3) {
-        if (p->plan.mbe == 4) return launch_eval_t<4, 2, 0, false, true>(p, a, ncand, st);
-        if (p->plan.mbe == 2) return launch_eval_t<2, 2, 0, false, true>(p, a, ncand, st);
-        if (p->plan.mbe == 1) return launch_eval_t<1, 2, 0, false, true>(p, a, ncand, st);
-    }
-#define EV_CASE(M, N) if (p->plan.mbe == M && p->plan.nrbw == N) return launch_eval_t<M, N>(p, a, ncand, st);
-    EV_CASE(4, 1) EV_CASE(4, 2) EV_CASE(4, 4) EV_CASE(4, 8)
-    EV_CASE(2, 1) EV_CASE(2, 2) EV_CASE(2, 4) EV_CASE(2, 8)
-    EV_CASE(1, 1) EV_CASE(1, 2) EV_CASE(1, 4) EV_CASE(1, 8)
-#undef EV_CASE
-    return hipErrorInvalidValue;
+    const Tuning& tu = p->tune;
+    const EvalLaunch fn = eval_build(eval_key(plan_facts(p->plan), a.tab.dtype, tu.eval_no_x16, tu.eval_no_msplit, tu.eval_no_b3)).fn;
+    return fn ? fn(p, a, ncand, st) : hipErrorInvalidValue;
 }
 
 // The rest of the host side — host-only headers, included like plan.hip.h — and the C ABI over it

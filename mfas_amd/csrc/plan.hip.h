@@ -743,3 +743,12 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
     }
     return plan_layout_as(hp, confs, n_cells, drop_seeds, K, chunk_cols, n_cus, allow_persist, tu, true, pl);
 }
+
+// what the choice of a launch's build reads from the plan (builds.hip.h)
+static PlanFacts plan_facts(const LayoutPlan& pl) {
+    PlanFacts f;
+    f.wide = pl.wide; f.MB = pl.g.MB; f.lean_chain = pl.lean_chain; f.same_group = pl.same_group; f.chain_split = pl.chain_split;
+    f.ngroups = (int)pl.groups.size(); f.nontemporal = pl.nontemporal; f.persist = pl.persist; f.res_wide = pl.res_wide; f.res_nu = pl.res_nu;
+    f.mbe = pl.mbe; f.nrbw = pl.nrbw; f.nrb = pl.g.nrb;
+    return f;
+}

@@ -103,20 +103,6 @@ struct ProfBracket {
     }
 };
 
-// The build that carries a launch with a sweep in it, over the plan and the record.  nch: candidates of its chain (0: none); same:
-// chain(g, t) and sweep(g, t) in ONE launch behind per-cell flags; split: the chain blocks are chain_split parts
-static StepBuild pick_step_kernel(const LayoutPlan& pl, const Launch& L, unsigned nch, bool same, bool split) {
-    const int MB = pl.g.MB;
-    if (pl.wide) return wide_sweep_build(pl.nontemporal);      // launch per phase only: the sweep of the one group, after its chain's launch
-    if (same) return same_build(MB, pl.nontemporal, split ? pl.chain_split : 1);
-    if (split) return step_build(MB, pl.nontemporal, 4, false, pl.chain_split);
-    // MB == 2: the two-workgroups-per-CU build unless a co-scheduled chain would bound the launch (see SweepU)
-    // (lean chain: the 128-VGPR build spills 8 registers of the element-parallel chain to scratch and is still the faster
-    //  one — R=16, B=20, 50 / 128 / 512 candidates: 47.2 / 99.2 / 418 us per step against 50.5 / 117.4 / 447 for the 2-workgroup build)
-    const bool occ = nch == 0 || pl.groups[L.sweep_g].alg_state > pl.occ_bytes;
-    return step_build(MB, pl.nontemporal, MB == 1 || (MB == 2 && (occ || pl.lean_chain)) ? 4 : 2, pl.lean_chain, 1);
-}
-
 // one record of the launch list -> one launch of epoch ep: the step-dependent arguments (positions and valid rows, step scalars, flag
 // target, exchange parity, gather parities), the build, the launch
 static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
@@ -164,7 +150,7 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
     }
     st.nchain = (int)nch;
     if (nsw == 0) {   // chain only: the latency-tuned standalone kernel (wide populations: theirs)
-        launch_build(p, pl.wide ? wide_chain_build() : chain_build(pl.g.MB, pl.lean_chain), nch, pl.lds_chain, p->stream, st.ca);
+        launch_build(p, chain_build(chain_key(plan_facts(pl))), nch, pl.lds_chain, p->stream, st.ca);
         return;
     }
     // algorithmic HBM bytes of this group's update+forward sweep: 24 B/param + the batch's taps + labels
@@ -180,7 +166,8 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
         st.sa.flag_target = st.ca.flag_target = (split ? (uint32_t)pl.chain_split : 1u) * ((uint32_t)st.ca.gstep + 1u);
         st.sa.flag_status = p->d_status;
     }
-    launch_build(p, pick_step_kernel(pl, L, nch, same, split), (unsigned)st.nchain + st.ga.nblocks + nsw, split ? pl.lds_split : pl.lds_step, p->stream, st);
+    const BuildKey key = step_key(plan_facts(pl), nch, same, pl.groups[gs].alg_state > pl.occ_bytes);
+    launch_build(p, step_build(key), (unsigned)st.nchain + st.ga.nblocks + nsw, split ? pl.lds_split : pl.lds_step, p->stream, st);
     if (same) { st.sa.cellflag = nullptr; st.ca.cellflag = nullptr; }
 }
 
@@ -212,11 +199,9 @@ static hipError_t persist_epoch_once(TrainCall& c, int ep, int64_t T) {
         // algorithmic bytes of the launch: T update+forward sweeps of every candidate
         ProfBracket prof(c, p->profiling, (double)T * (pl.groups[0].alg_state + pl.groups[0].alg_feat * c.elt() + 8.0 * c.B * K));
         const int lw = (int)(pl.lds_president / 4) - PERSIST_LDS_WORDS;
-        // the search default — no BatchNorm, no alphas, single-task softmax CE — runs the chain compiled for exactly that (chain_lean PLAIN)
-        // (round 6: and `--batchnorm` alone, main_searchable_ntu.py:48 of the reference, the chain compiled for exactly THAT — PLAIN = 2)
-        const bool simple = !g.alphas && !g.multitask && g.loss_mode == 0 && !p->tune.no_plain_chain;
-        const bool x16 = c.train->dtype != MFAS_DT_F32;
-        launch_build(p, president_build(g.MB, x16, x16 && pl.res_wide, pl.res_nu, simple ? (g.bn ? 2 : 1) : 0), grid, pl.lds_president, p->stream, pa, lw);
+        // (PLAIN = 2: `--batchnorm` alone, main_searchable_ntu.py:48 of the reference)
+        const int plain = president_plain(g.alphas, g.multitask, g.loss_mode, g.bn, p->tune.no_plain_chain);
+        launch_build(p, president_build(president_key(plan_facts(pl), c.train->dtype != MFAS_DT_F32, plain)), grid, pl.lds_president, p->stream, pa, lw);
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -525,7 +510,7 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
     if (!pl.wide)
         for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) lds_need = std::max(lds_need, sweep_unit_lds(g, pl.descs[j]));
     if (lds_need > 150 * 1024) return fail(MFAS_EINVAL, "train-mode forward: this population's units are too wide for the streaming kernels");
-    const StepKernel sweep_k = pl.wide ? wide_sweep_kernel(false) : step_kernel(g.MB, false, g.MB == 1 ? 4 : 2, false, 1);
+    const StepKernel sweep_k = step_build(single_batch_step_key(plan_facts(pl))).fn;
     if (lds_need > pl.lds_step) HIPCHK(set_lds(sweep_k, lds_need));
     auto sweep = [&]() { launch(sweep_k, nsw, lds_need, p->stream, st); };
     if (dlogits) {
@@ -539,7 +524,7 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
     sweep();
     // 2. the chain (running statistics move like in any train-mode forward): stops at the logits, or goes on from the caller's dL/dlogits and leaves dy_i for the sweep
     st.ca = ca;
-    launch(pl.wide ? wide_chain_kernel() : chain_kernel(g.MB, pl.lean_chain), 1u, pl.lds_chain, p->stream, st.ca);
+    launch(chain_build(single_batch_chain_key(plan_facts(pl))).fn, 1u, pl.lds_chain, p->stream, st.ca);
     if (dlogits) {   // 3. dW of every matrix into its m slot (see the header comment); W, v-scaled-by-lr-0 steps leave W as it was
         st.sa.do_update = 1; st.sa.do_forward = 0;
         sweep();

@@ -14,7 +14,7 @@
 tests/test_axes_cpu.py holds the designs, the seeds and the inputs (shared by import) and keeps the float32 oracle under a quarter
 of every tau on exactly these inputs.  Same rule, same taus as the sibling files: |got - ref64| <= tau 2^-24 M elementwise
 (logits 6, gradients 20, running statistics 4; train steps: m 20, v 1, w 20, runstat 4, loss 1); every population's schedule is
-asserted by name with pop.schedule(), the resident one's k_president build with president_build.
+asserted by name with pop.schedule(), the resident one's k_president build with the library's launch record.
 
 Run on its own, with a time limit:  python -m pytest tests/test_gpu_axes_ref64.py -m gpu -x -q -s
 
@@ -152,10 +152,9 @@ def test_population_steps_vs_ref64(dev, spec):
     rec = key if axis == "scalar" else axis
     pop = GT.schedule_pop(name, inp, dev, entry=entry)          # (asserts the schedule with pop.schedule())
     try:
-        if name == "persistent":
-            build = GR.president_build(ehp, inp["dtype"], GR.resident_schedule(ehp, confs, entry[4], pop.schedule(), dev))
-            assert build is not None and build.startswith(f"mb2-plain{2 if hp.bn else 1}-x16"), (pid, build)
         S, ST = GT.engine_states(pop, G.gpu_table(inp["t"], inp["dtype"], dev), p0s, inp["etas"], torch.from_numpy(inp["order"]).to(dev))
+        if name == "persistent":
+            GR.assert_president_record(pop, [f"mb2-plain{2 if hp.bn else 1}-{form}" for form in GR.FORMS if form.startswith("x16")], pid)
         if axis == "plain":
             check_population_entry_points(dev, pop, inp, pid, rec)
         if name == "persistent":

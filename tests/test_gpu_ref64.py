@@ -125,21 +125,20 @@ def eval_me(hp):
     return 16
 
 
-def eval_build(hp, dtype):
-    """The k_eval build the dev pass runs for this geometry and table dtype with no switch set, as (MBE, NRBW, split, 16-bit rows,
-    B3): plan_layout's row blocks per wave (1, 2, 4, 8: three take the build for four, five to seven the one for eight) and
-    launch_eval's order of choice (m-blocks split over the waves at one or two row blocks, 16-bit rows there over bf16 tables; the
-    bf16 x 3 build at two row blocks per wave over bf16 tables; else the plain build)."""
+def eval_facts(hp):
+    """What plan_layout hands the dev pass's choice of build (builds.hip.h: eval_key) for this geometry: batch tiles per workgroup,
+    row blocks per wave (1, 2, 4, 8: three take the build for four, five to seven the one for eight), row blocks."""
     nrb = -(-hp.R // 16)
     nrbw = (nrb + 3) // 4
     nrbw = 4 if nrbw == 3 else (8 if 4 < nrbw < 8 else nrbw)
-    mbe = eval_me(hp) // 16
-    bf16 = dtype == "bfloat16"
-    if nrbw == 1 and nrb <= 2:
-        return (mbe, 1, nrb, bf16, False)
-    if bf16 and nrbw == 2:
-        return (mbe, 2, 0, True, True)
-    return (mbe, nrbw, 0, False, False)
+    return dict(mbe=eval_me(hp) // 16, nrbw=nrbw, nrb=nrb)
+
+
+def eval_name(build):
+    """A k_eval build written (MBE, NRBW, split, 16-bit rows, B3) by the name of its instantiation, k_eval<MBE, NRBW, MSP, XB, B3>:
+    the bf16 x 3 build keeps its rows 16-bit by itself (XB is the split builds' argument)."""
+    mbe, nrbw, split, x16, b3 = build
+    return f"k_eval<{mbe},{nrbw},{split},{int(x16 and not b3)},{int(b3)}>"
 
 
 # ------------------------------------------------------------------------------------------------ GPU plumbing

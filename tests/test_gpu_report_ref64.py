@@ -1,9 +1,10 @@
 """What train() reports to the search controller, against the float64 reference (tests/ref64.py): the per-epoch dev statistics
 of a POPULATION call, the parameters snapshot_best leaves, and the status word.
 
-(a) Population dev pass.  REPORT_CASES names every k_eval build launch_eval can reach (tests/test_gpu_ref64.py::eval_build; the
-    builds no accepted geometry reaches are listed in UNREACHABLE_BUILDS with the reason) with K >= 9 heterogeneous candidates, so
-    that the bf16 x 3 build's 1-D grid takes its interleaved branch (full groups of eight candidates) and its remainder branch.
+(a) Population dev pass.  REPORT_CASES names every k_eval build the dev pass's choice can reach (builds.hip.h: eval_key, held to each
+    case's build by tests/test_report_cpu.py; the builds no accepted geometry reaches are listed in UNREACHABLE_BUILDS with the
+    reason) with K >= 9 heterogeneous candidates, so that the bf16 x 3 build's 1-D grid takes its interleaved branch (full groups of
+    eight candidates) and its remainder branch.
     E = 2 as two segments; column e of segment e of every candidate through check_dev against ref64 on that candidate's own
     parameters after that epoch.  The candidates' ref64 loss intervals are pairwise disjoint (asserted), so a slot or tile mix-up
     cannot pass.  tests/test_report_cpu.py checks the same conditions with oracle-trained parameters and makes five mutations of
@@ -76,7 +77,7 @@ REPORT_CASES = [
 ]
 REPORT_IDS = [c[0] for c in REPORT_CASES]
 
-# Every k_eval instantiation launch_eval names: EV_SPLIT, the three bf16 x 3 builds, EV_CASE.
+# Every k_eval instantiation of the table (builds.hip.h: BUILDS_EVAL_ROWS): the split builds, the three bf16 x 3 builds, the plain ones.
 ALL_BUILDS = ([(m, 1, s, x, False) for m in (4, 2, 1) for s in (1, 2) for x in (False, True)] + [(m, 2, 0, True, True) for m in (4, 2, 1)] +
               [(m, n, 0, False, False) for m in (4, 2, 1) for n in (1, 2, 4, 8)])
 # The tile is 64 rows unless (64 * (max(136, Cp + 4) + Rp + 8)) * 4 exceeds 80 KiB, i.e. Rp + max(136, Cp + 4) > 312, and 32 rows
@@ -223,12 +224,12 @@ def record(key, value):
 @pytest.mark.parametrize("case", REPORT_CASES, ids=REPORT_IDS)
 def test_population_dev_pass_vs_ref64(dev, case):
     """Two epochs as two segments: every candidate's dev statistics of epoch e against ref64 on its own parameters after epoch e,
-    the other column zero, the build the case was written for, and the conditions that make a slot or tile mix-up visible."""
+    the other column zero, and the conditions that make a slot or tile mix-up visible.  (The build the case was written for: the
+    record does not cover the dev pass, tests/test_report_cpu.py holds it without a device.)"""
     from tests.helpers import engine_hyper
     cid, R, C, B, dtype, K, extra, build = case
     inp = report_inputs(case)
     hp = inp["hp"]
-    assert G.eval_build(hp, dtype) == build, (cid, G.eval_build(hp, dtype))
     pop = make_population(engine_hyper(hp), inp["confs"], dev, inp["seeds"], pos_weight=G.pos_weight(hp) if hp.loss_mode else None)
     try:
         for k, p in enumerate(inp["p0s"]):

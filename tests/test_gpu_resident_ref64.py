@@ -5,9 +5,10 @@ The resident loop is the schedule the search runs (R <= 16, B = 20, 6-16 candida
 whole launch, stages the rows of batch t + 2 right after step t and stores the state back only at the launch's end; its kernel is
 built thirty times: MB in {1, 2} x PLAIN in {0 general chain, 1 search default, 2 BatchNorm alone} x five unit forms (f32 staging
 with one or two units per workgroup, 16-bit staging with one or two, one 16-bit WIDE unit of up to 1024 columns).  RESIDENT_BUILDS
-has one row per build; president_build() restates the launch's choice (train.hip.h: persist_epoch_once) and every test asserts the
-build its id names before it trains, and that the population still runs the resident schedule afterwards (a launch whose grid was
-not resident at once would have handed the population to launch-per-phase).
+has one row per build; every test asserts that the library's own launch record (Population.launch_record()) names the build its id
+spells (president_name) and nothing else after it has trained, and that the population still runs the resident schedule afterwards (a
+launch whose grid was not resident at once would have handed the population to launch-per-phase).  tests/test_resident_cpu.py holds
+the same ids to the choice of builds.hip.h (president_key) without a device.
 
 The train table has N = 5 B + r rows (nb = 6 batches) and steps (1, 2, 3, 5, 6, 7) are checked: 1..3 as in the sibling files
 (batch 0, batch 1, batch 2 — the first whose rows were staged inside the step loop), step 5 the fifth full batch of one launch (rows
@@ -134,23 +135,18 @@ def row_order_mode(rid):
     return ("shared", "per_candidate")[BUILD_IDS.index(rid) % 2]
 
 
-def president_build(hp, dtype, sched):
-    """The k_president instantiation a train() call of this population launches, as the id of its RESIDENT_BUILDS row, or None when
-    the population does not run the resident schedule.  A restatement of the launch's choice (train.hip.h, persist_epoch_once):
-    simple = no alphas, no multitask, the single-label head (no test sets MFAS_NO_PLAIN_CHAIN); x16 = the table is not f32;
-    wide = x16 and the plan's widest resident unit has more than 512 columns; nu = the plan's units per workgroup.
-    hp: the engine's Hyper; sched: pop.schedule() or plan_population()'s answer, with "widest_unit" (resident_schedule)."""
-    if not (sched["persistent"] and sched["resident_units"] > 0):
-        return None
-    mb = -(-hp.B // 16)
-    simple = not hp.alphas and not hp.multitask and hp.loss_mode == 0
-    plain = (2 if hp.bn else 1) if simple else 0
-    x16 = dtype != "float32"
-    if x16 and sched["widest_unit"] > 512:
-        form = "x16-wide"
-    else:
-        form = f"{'x16' if x16 else 'f32'}-nu{sched['units_per_workgroup']}"
-    return f"mb{mb}-plain{plain}-{form}"
+def president_name(rid):
+    """The launch record's name of a RESIDENT_BUILDS row: k_president<MB, tiles per wave, 16-bit staging, units per workgroup, PLAIN> —
+    four tiles per wave (PERSIST_NTR), eight for the wide unit (PERSIST_NTR16)."""
+    mb, plain, form = rid.split("-", 2)
+    ntr, x16, nu = {"f32-nu1": (4, 0, 1), "f32-nu2": (4, 0, 2), "x16-nu1": (4, 1, 1), "x16-nu2": (4, 1, 2), "x16-wide": (8, 1, 1)}[form]
+    return f"k_president<{mb[2:]},{ntr},{x16},{nu},{plain[5:]}>"
+
+
+def assert_president_record(pop, rids, tag):
+    """The library's record of the population's last train call: one of the builds `rids` name, launched, and nothing else."""
+    rec = pop.launch_record()
+    assert len(rec) == 1 and set(rec) <= {president_name(r) for r in rids} and all(n > 0 for n in rec.values()), (tag, rec)
 
 
 def resident_schedule(hp, confs, chunk_cols, sched=None, device="cuda:0"):
@@ -202,10 +198,9 @@ def test_resident_builds_steps_vs_ref64(dev, row):
     try:
         if hp.loss_mode == 1:
             pop.set_pos_weight(G.pos_weight(hp))
-        sched = resident_schedule(ehp, confs, cc, pop.schedule(), dev)
-        assert president_build(ehp, dtype, sched) == rid, (rid, sched)
         tab = G.gpu_table(t, dtype, dev)
         S, ST = GT.engine_states(pop, tab, p0s, inp["etas"], torch.from_numpy(inp["order"]).to(dev), STEPS)
+        assert_president_record(pop, [rid], rid)
         stats = None
         if rid in DEV_ROWS:
             for k, p0 in enumerate(p0s):
@@ -213,6 +208,7 @@ def test_resident_builds_steps_vs_ref64(dev, row):
             tdv = G.case_table(base_case(row), hp, G.N_EVAL, inp["seed"] + 2, dtype)
             stats, status = pop.train(tab, G.gpu_table(tdv, dtype, dev), 1, O.eta_sequence(1e-3, 1e-6, 1, 2, inp["N"] / hp.B, FULL + 1))
             assert not status.any(), (rid, status)
+            assert_president_record(pop, [rid], rid)
             after = [G.state_np(pop, k) for k in range(len(confs))]
         assert pop.schedule()["persistent"] == 1, (rid, "a resident launch was given up: the steps ran launch per phase")
     finally:

@@ -1,7 +1,7 @@
 """Every launch-per-phase sweep build — k_step, k_step_same, k_sweep_wide, each cached (NT = 0) and nontemporal (NT = 1) — against
 the float64 reference (tests/ref64.py), one step at a time and element by element, and each asserted by the name the LIBRARY gives
 it: Population.launch_record() (mfas_population_launch_record) is filled where the launches are made, from the same template
-instantiation the function pointer comes from, so a wrong row in a kernel table or a wrong choice in pick_step_kernel shows.
+instantiation the function pointer comes from, so a wrong row in a kernel table or a wrong choice in step_key (builds.hip.h) shows.
 
 Which of the two builds of a form runs is decided by population size (plan.hip.h: planes above 200 MiB stream nontemporally), which
 no other elementwise test reaches: they all run the cached builds.  Here every row of SWEEP_FORMS (tests/test_step_builds_cpu.py:
@@ -18,8 +18,8 @@ natural_nt, 17.7 M floats per plane = 212 MB > 200 MiB, whose record must name k
 same population with one cell fewer (202 MB) names k_step<1,0,4,0,1>; natural_occ, B = 17, twelve candidates in two groups of 250.4 MB
 of state each (> occ_bytes = 250 MB), whose record must name k_step<2,1,4,0,1> with a chain in the launch and no WPE = 2 build.
 
-tests/test_step_builds_cpu.py holds the inputs, the coverage argument (22 of the 24 instantiations are reachable; k_step<2,.,2,1,1>
-is not), the float32 oracle's calibration on exactly these inputs and the mutations (a tile's dropped store of m / v / W, a tile
+tests/test_step_builds_cpu.py holds the inputs, the coverage argument (all 22 instantiations are reachable), the float32 oracle's
+calibration on exactly these inputs and the mutations (a tile's dropped store of m / v / W, a tile
 updated twice).
 
 Worst ratio over all steps, candidates and elements of a family (-s prints the run's table; the CPU column is the float32 oracle on
@@ -37,9 +37,8 @@ v 1.01, w 1.18 (k_sweep_wide), runstat 1.00, loss 1.5 (0.002 against 0.001 of a 
 are bit-identical and every record names the builds its row lists, so the cached runs have the same figures.  Nothing had to change
 in a kernel or in the dispatch.
 
-test_resident_record_names_the_president_build closes the same gap for the resident loop: test_gpu_resident_ref64.py asserts its
-thirty builds through a Python restatement of the launch's choice (president_build); here the library's record of a two-step call
-of each of those populations must name that k_president build and nothing else.
+test_resident_record_names_the_president_build does the same for the resident loop: the library's record of a two-step call of each
+of test_gpu_resident_ref64.py's thirty populations must name that k_president build and nothing else.
 
 Measured on an MI355X (43 tests, 8.4 s for the file on its own, 1.4 s of it the first test's device start-up): a SWEEP_FORMS row
 0.04 - 0.52 s (two populations x eight train calls, then ref64 for three candidates x six steps on the CPU), natural_nt 1.8 s,
@@ -204,19 +203,11 @@ def test_natural_thresholds_vs_ref64(dev, name):
             pop.close()
 
 
-def president_name(rid):
-    """The record's name of a RESIDENT_BUILDS row (tests/test_gpu_resident_ref64.py): k_president<MB, tiles per wave, 16-bit staging,
-    units per workgroup, PLAIN> — four tiles per wave (PERSIST_NTR), eight for the wide unit (PERSIST_NTR16)."""
-    mb, plain, form = rid.split("-", 2)
-    ntr, x16, nu = {"f32-nu1": (4, 0, 1), "f32-nu2": (4, 0, 2), "x16-nu1": (4, 1, 1), "x16-nu2": (4, 1, 2), "x16-wide": (8, 1, 1)}[form]
-    return f"k_president<{mb[2:]},{ntr},{x16},{nu},{plain[5:]}>"
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("row", GR.RESIDENT_BUILDS, ids=GR.BUILD_IDS)
 def test_resident_record_names_the_president_build(dev, row):
-    """The thirty resident builds are asserted in test_gpu_resident_ref64.py through a restatement of the launch's choice; here the
-    library's own record of a two-step call of the same population must name that build and nothing else."""
+    """The library's own record of a two-step call of each of test_gpu_resident_ref64.py's thirty populations names the build the
+    row's id spells and nothing else."""
     torch = G._torch()
     from mfas_amd import Population
     rid, cc = row[0], row[9]
@@ -233,4 +224,4 @@ def test_resident_record_names_the_president_build(dev, row):
         assert not status.any() and pop.schedule()["persistent"] == 1, (rid, status)
     finally:
         pop.close()
-    assert set(rec) == {president_name(rid)} and all(n > 0 for n in rec.values()), (rid, rec)
+    assert set(rec) == {GR.president_name(rid)} and all(n > 0 for n in rec.values()), (rid, rec)

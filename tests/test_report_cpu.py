@@ -5,7 +5,8 @@
 * the conditions that keep the comparison from hiding a failure (pairwise disjoint loss intervals, the ambiguity cap, the
   multi-label count windows) hold for the reference alone;
 * five mutations of the per-candidate report (a restatement of k_eval's 1-D grid map) fail check_dev on some candidate;
-* every dev-pass build launch_eval can reach is named by a case, the others are listed with the reason;
+* every dev-pass build the library's choice (builds.hip.h: eval_key, compiled by tests/builds_header.py) can reach is named by a
+  case, the others are listed with the reason;
 * the host bookkeeping (best_dev_accuracy, best_dev_f1) against a restatement of the reference's loops, and the best-epoch rule.
 """
 import functools
@@ -14,6 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import np_oracle as O
+from tests import builds_header as BH
 from tests import ref64 as R64
 from tests import test_gpu_ref64 as G
 from tests import test_gpu_report_ref64 as RP
@@ -153,20 +155,28 @@ def test_report_mutation_fails_check_dev(mutation):
 
 
 # ------------------------------------------------------------------------------------------------ coverage of the builds
+def eval_choice(facts_and_dtypes):
+    """builds.hip.h's eval_key with no switch set, for (eval facts, table dtype) pairs: the names of the builds."""
+    return BH.ask([("eval", BH.facts(**f), BH.DTYPE[dtype], 0, 0, 0) for f, dtype in facts_and_dtypes])
+
+
 def test_every_reachable_dev_pass_build_is_named_by_a_case():
-    reachable = set()
+    geometries = set()
     for R in range(1, 513):
         for C in range(1, 257, 5):
-            hp = O.Hyper(R=R, C=C, B=16, s_sizes=G.W_A["s"], v_sizes=G.W_A["v"])
-            reachable |= {G.eval_build(hp, dtype) for dtype in G.DTYPES}
+            geometries.add(tuple(sorted(G.eval_facts(O.Hyper(R=R, C=C, B=16, s_sizes=G.W_A["s"], v_sizes=G.W_A["v"])).items())))
+    reachable = set(eval_choice([(dict(f), dtype) for f in sorted(geometries) for dtype in G.DTYPES]))
     hp = O.Hyper(R=512, C=256, B=16, s_sizes=G.W_A["s"], v_sizes=G.W_A["v"])
     assert G.eval_me(hp) == 16
-    named = {c[7] for c in RP.REPORT_CASES}
+    all_builds = {G.eval_name(b) for b in RP.ALL_BUILDS}
+    named = {G.eval_name(c[7]) for c in RP.REPORT_CASES}
     assert reachable == named, (sorted(reachable - named), sorted(named - reachable))
-    assert set(RP.ALL_BUILDS) - reachable == set(RP.UNREACHABLE_BUILDS), sorted(set(RP.ALL_BUILDS) - reachable - set(RP.UNREACHABLE_BUILDS))
-    assert reachable <= set(RP.ALL_BUILDS) and len(set(RP.ALL_BUILDS)) == len(RP.ALL_BUILDS) == 27
-    for case in RP.REPORT_CASES:
-        assert G.eval_build(RP.report_hyper(case), case[4]) == case[7], case[0]
+    assert all_builds - reachable == {G.eval_name(b) for b in RP.UNREACHABLE_BUILDS}, sorted(all_builds - reachable)
+    assert reachable <= all_builds and len(all_builds) == len(RP.ALL_BUILDS) == 27
+    assert all_builds == {k for k in BH.ask1("tables", None) if k.startswith("k_eval<")}          # the library's table
+    cases = eval_choice([(G.eval_facts(RP.report_hyper(case)), case[4]) for case in RP.REPORT_CASES])
+    for case, name in zip(RP.REPORT_CASES, cases):
+        assert name == G.eval_name(case[7]), (case[0], name)
     # the branches of the 1-D grid: a full group with a remainder, full groups only, a remainder of one
     b3 = {c[0]: c[5] for c in RP.REPORT_CASES if c[7][4]}
     assert b3["b3_k11"] == 11 and b3["b3_k16_mt"] == 16 and b3["b3_r72_k9"] == 9 and all(K >= 9 for K in b3.values())

@@ -2,7 +2,8 @@
 other train schedules on the GPU):
 
 * coverage: RESIDENT_BUILDS names exactly the thirty (MB, PLAIN, unit form) builds of k_president, every row's hyper-parameters,
-  table dtype and plan (the layout query, a pure host function: 256 compute units without a device) give the build its id names,
+  table dtype and plan (the layout query, a pure host function: 256 compute units without a device) give the build its id names
+  through the choice of builds.hip.h itself (president_plain, president_key: compiled with g++ by tests/builds_header.py),
   and the table spans what the design asks for (batch sizes, the three ways into the general chain, depths, nonlinearities, widths);
 * calibration: on every row's own inputs and on the late steps of the other schedules the float32 oracle stays under a quarter of
   each tau the GPU test applies (-s prints the worst ratios per group, the figures quoted in the GPU file's docstring);
@@ -11,6 +12,7 @@ other train schedules on the GPU):
 import numpy as np
 import pytest
 
+from tests import builds_header as BH
 from tests import test_gpu_ref64 as G
 from tests import test_gpu_resident_ref64 as GR
 from tests import test_gpu_train_ref64 as GT
@@ -84,6 +86,23 @@ def test_table_names_the_thirty_builds():
     assert sorted(parse(r)[1] for r in GR.DEV_ROWS) == [0, 1, 2] and set(GR.DEV_ROWS) <= set(GR.BUILD_IDS)
 
 
+def president_queries(hp, dtype, sched):
+    """The two questions a resident launch asks builds.hip.h, from the launch's inputs (train.hip.h: persist_epoch_once): the chain
+    variant of the hyper-parameters (no test sets MFAS_NO_PLAIN_CHAIN), and the build for the plan's facts — batch tiles, units per
+    workgroup, a widest resident unit of more than 512 columns — and a table that is or is not f32.
+    hp: the engine's Hyper; sched: pop.schedule() or plan_population()'s answer, with "widest_unit" (GR.resident_schedule)."""
+    f = BH.facts(persist=bool(sched["persistent"] and sched["resident_units"] > 0), MB=-(-hp.B // 16), lean=1,
+                 res_wide=sched["widest_unit"] > 512, res_nu=sched["units_per_workgroup"])
+    return f, ("plain", None, hp.alphas, hp.multitask, hp.loss_mode, hp.bn, 0), dtype != "float32"
+
+
+def header_president(hp, dtype, sched):
+    """The k_president build a train() call of this population launches, by the record's name, as builds.hip.h chooses it."""
+    f, plain_q, x16 = president_queries(hp, dtype, sched)
+    assert f["persist"], sched
+    return BH.ask1("president", f, x16, BH.ask([plain_q])[0])
+
+
 @pytest.mark.parametrize("row", GR.RESIDENT_BUILDS, ids=GR.BUILD_IDS)
 def test_row_plans_as_the_build_its_id_names(row):
     """The layout query at 256 compute units: resident, the id's units per workgroup and unit width; with the row's
@@ -96,7 +115,7 @@ def test_row_plans_as_the_build_its_id_names(row):
     sched = GR.resident_schedule(ehp, confs, cc)
     if sched["compute_units"] != 256:       # (a device of another size answers for itself: the GPU test asserts the build there)
         return
-    assert GR.president_build(ehp, dtype, sched) == rid, (rid, sched)
+    assert header_president(ehp, dtype, sched) == GR.president_name(rid), (rid, sched)
     assert sched["resident_workgroups"] == -(-sched["resident_units"] // sched["units_per_workgroup"])
     assert K + sched["resident_workgroups"] <= 256 and K <= 64, sched
     if rid.endswith("nu2"):
@@ -108,8 +127,8 @@ def test_row_plans_as_the_build_its_id_names(row):
 
 
 def test_president_build_restates_the_launch():
-    """president_build over the launch's inputs (train.hip.h: persist_epoch_once): every build is reachable, and a population that
-    is not resident has none."""
+    """builds.hip.h's president_key over the launch's inputs: every one of the thirty builds is reachable and nothing else, each is
+    among the builds its plan may launch (plan_keys), and a population that is not resident may launch none."""
     from mfas_amd import Hyper
     seen = set()
     for B in (16, 20):
@@ -119,10 +138,13 @@ def test_president_build_restates_the_launch():
                 for nu in (1, 2):
                     for widest in (256, 1008):
                         s = dict(persistent=1, resident_units=9, units_per_workgroup=nu, widest_unit=widest)
-                        seen.add(GR.president_build(hp, dtype, s))
-                        assert GR.president_build(hp, dtype, dict(s, persistent=0)) is None
-                        assert GR.president_build(hp, dtype, dict(s, resident_units=0)) is None
-    assert seen == set(GR.ALL_BUILDS), seen ^ set(GR.ALL_BUILDS)
+                        name = header_president(hp, dtype, s)
+                        f = president_queries(hp, dtype, s)[0]
+                        assert name in BH.ask1("plan", f), (name, f)
+                        seen.add(name)
+                        for off in (dict(s, persistent=0), dict(s, resident_units=0)):
+                            assert not any(k.startswith("k_president") for k in BH.ask1("plan", president_queries(hp, dtype, off)[0])), off
+    assert seen == {GR.president_name(b) for b in GR.ALL_BUILDS} and len(seen) == 30, seen ^ {GR.president_name(b) for b in GR.ALL_BUILDS}
 
 
 # ------------------------------------------------------------------------------------------------ calibration

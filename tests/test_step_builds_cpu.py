@@ -3,15 +3,15 @@ k_sweep_wide, cached (NT = 0) and nontemporal (NT = 1) — to the float64 refere
 launch record gives it (mfas_population_launch_record).  This file holds the inputs of both (shared by import) and checks, without
 a device:
 
-* coverage: ALL_BUILDS restates the three kernel tables of mfas_hip.hip (16 + 6 + 2 instantiations; the source is parsed and compared),
-  pick_step_kernel() restates the launch's choice (train.hip.h: pick_step_kernel, lines 106-118) over the plan states plan_layout can
-  produce (plan.hip.h:530-549: the lean chain has B <= 32 and neither a same-group launch nor chain_split; the same-group launch has
-  B <= 32; chain_split has B <= 16), every build the choice can reach appears in SWEEP_FORMS x {cached, nontemporal}, and UNREACHABLE
-  lists the rest with the reason;
-* every row's expected record follows from the row's plan facts through that restatement and the launch list (launches.hip.h);
+* coverage: ALL_BUILDS is the three sweep tables of the library (14 + 6 + 2 instantiations: the key list builds.hip.h compiles into
+  them, printed by tests/builds_header.py's program), the launch's choice is the header's own step_key / chain_key, asked over the plan
+  states plan_layout can produce (plan_layout: the lean chain has B <= 32 and neither a same-group launch nor chain_split; the
+  same-group launch has B <= 32; chain_split has B <= 16), every build the choice can reach appears in SWEEP_FORMS x {cached,
+  nontemporal}, and UNREACHABLE — now empty — would list the rest with the reason;
+* every row's expected record follows from the row's plan facts through the header's choice and the launch list (launches.hip.h);
 * calibration: on every row's own inputs the float32 oracle stays under a quarter of each tau, the train counts lie inside [lo, hi],
   and ref64 alone leaves at most a quarter of a step's rows ambiguous (the rule and the cap of tests/test_axes_cpu.py);
-* the sizes of the two natural populations against the thresholds they are sized by (plan.hip.h:730 and :673);
+* the sizes of the two natural populations against the thresholds they are sized by (plan_layout's nontemporal and occ_bytes);
 * power: a weight tile whose store of m, of v or of W is dropped at step 2, and a tile that is updated twice at step 2, exceed a tau
   at a checked step on one row of each kernel family.
 
@@ -27,11 +27,11 @@ moves step 1.
 -s prints the oracle's worst ratios per kernel family: the CPU figures quoted in the GPU file's docstring.
 """
 import os
-import re
 
 import numpy as np
 import pytest
 
+from tests import builds_header as BH
 from tests import test_gpu_ref64 as G
 from tests import test_gpu_resident_ref64 as GR
 from tests import test_gpu_train_ref64 as GT
@@ -64,8 +64,8 @@ def note(group, r):
 
 
 # ------------------------------------------------------------------------------------------------ the kernel tables
-# mfas_hip.hip: step_build's rows (MB, WPE, LEAN, NS), same_build's rows (MB, NS), each built cached and nontemporal; the wide sweep
-STEP_ROWS = [(1, 4, 0, 4), (1, 4, 0, 1), (2, 2, 0, 1), (2, 4, 0, 1), (4, 2, 0, 1), (1, 4, 1, 1), (2, 2, 1, 1), (2, 4, 1, 1)]
+# builds.hip.h: BUILDS_STEP_ROWS (MB, WPE, LEAN, NS), BUILDS_SAME_ROWS (MB, NS), each built cached and nontemporal; the wide sweep
+STEP_ROWS = [(1, 4, 0, 4), (1, 4, 0, 1), (2, 2, 0, 1), (2, 4, 0, 1), (4, 2, 0, 1), (1, 4, 1, 1), (2, 4, 1, 1)]
 SAME_ROWS = [(1, 1), (2, 1), (1, 4)]
 # a build's name as the launch record spells it, with N for the NT argument
 ALL_FORMS = [f"k_step<{m},N,{w},{f},{s}>" for m, w, f, s in STEP_ROWS] + [f"k_step_same<{m},N,{s}>" for m, s in SAME_ROWS] + ["k_sweep_wide<N>"]
@@ -76,28 +76,12 @@ def named(form, nt):
 
 
 ALL_BUILDS = [named(f, nt) for f in ALL_FORMS for nt in (0, 1)]
-# a form no plan reaches: pick_step_kernel gives a lean chain's launch WPE = 4 whenever MB == 2 (`occ || pl.lean_chain`), and the lean
-# chain exists only at MB <= 2, so the 2-waves build of the lean chain is built (and set_lds_all sets its LDS limit) but never launched
-UNREACHABLE = {"k_step<2,N,2,1,1>": "lean chain at MB = 2 always takes WPE = 4 (train.hip.h:117)"}
-
-
-def pick_step_kernel(wide, MB, lean, chain_split, nch, same, over_occ):
-    """train.hip.h:106-118, the form (NT left open: pl.nontemporal goes into every branch unchanged).  nch: candidates of the
-    launch's chain; same: the same-group launch of a step; over_occ: the sweep group's state is above occ_bytes."""
-    split = bool(chain_split) and nch > 0
-    if wide:
-        return "k_sweep_wide<N>"
-    if same:
-        return f"k_step_same<{MB},N,{chain_split if split else 1}>"
-    if split:
-        return f"k_step<{MB},N,4,0,{chain_split}>"
-    occ = nch == 0 or over_occ
-    wpe = 4 if MB == 1 or (MB == 2 and (occ or lean)) else 2
-    return f"k_step<{MB},N,{wpe},{int(lean)},1>"
+# a form no plan reaches, with the reason: none since k_step<2,N,2,1,1> (a lean chain's launch at MB = 2 always takes WPE = 4) left the table
+UNREACHABLE = {}
 
 
 def plan_states():
-    """Every (wide, MB, lean, same_group, chain_split, groups) plan_layout can produce (plan.hip.h:223, :530-549)."""
+    """Every (wide, MB, lean, same_group, chain_split, groups) plan_layout can produce."""
     out = [dict(wide=True, MB=MB, lean=False, same_group=False, chain_split=0, groups=1) for MB in (1, 2, 4)]
     for MB in (1, 2, 4):
         for lean in (False, True):
@@ -114,44 +98,56 @@ def plan_states():
     return out
 
 
-def launch_forms(st, over_occ):
-    """The builds of one epoch's launches for a plan state (launches.hip.h: epoch_launches; train.hip.h: launch_record), chain builds
-    included: a launch without a sweep is the standalone chain, the prologue and a two-group epoch's last launch carry no chain."""
-    chain = "k_chain_wide" if st["wide"] else f"k_chain<{st['MB']},{int(st['lean'])}>"
-    pick = lambda nch, same: pick_step_kernel(st["wide"], st["MB"], st["lean"], st["chain_split"], nch, same, over_occ)  # noqa: E731
-    forms = {pick(0, False)}                        # the prologue: forward sums of batch 0
+def launch_inputs(st):
+    """What the launches of one launch-per-phase epoch hand the choice (launches.hip.h: epoch_launches; train.hip.h: launch_record):
+    (has a sweep, has a chain, same-group launch).  The prologue, and a two-group epoch's last launch, are sweeps without a chain; a
+    launch without a sweep is the standalone chain."""
     if st["same_group"]:
-        forms.add(pick(1, True))
-    elif st["groups"] == 1:
-        forms |= {chain, pick(0, False)}
-    else:
-        forms |= {chain, pick(1, False), pick(0, False)}
-    return forms
+        return [(1, 0, 0), (1, 1, 1)]
+    if st["groups"] == 1:
+        return [(1, 0, 0), (0, 1, 0)]
+    return [(1, 0, 0), (0, 1, 0), (1, 1, 0)]
+
+
+def form_of(cached, nontemporal):
+    """The two names the header gives a launch under NT = 0 and NT = 1, as one form: they differ in the NT argument alone."""
+    if cached == nontemporal:
+        return cached
+    d = [i for i, (a, b) in enumerate(zip(cached, nontemporal)) if a != b]
+    assert len(cached) == len(nontemporal) and len(d) == 1 and (cached[d[0]], nontemporal[d[0]]) == ("0", "1"), (cached, nontemporal)
+    return cached[:d[0]] + "N" + cached[d[0] + 1:]
+
+
+def launch_forms(st, over_occ):
+    """The builds of one epoch's launches for a plan state as builds.hip.h chooses them (step_key, chain_key), chain builds included."""
+    plan = {k: st[k] for k in ("wide", "MB", "lean", "same_group", "chain_split", "groups")}
+    queries = []
+    for nt in (0, 1):
+        f = BH.facts(nt=nt, **plan)
+        queries += [("step", f, 3 * chain, same, over_occ) if sweep else ("chain", f) for sweep, chain, same in launch_inputs(st)]
+    names = BH.ask(queries)
+    n = len(names) // 2
+    return {form_of(a, b) for a, b in zip(names[:n], names[n:])}
 
 
 def test_tables_are_the_sources():
-    """ALL_BUILDS is what mfas_hip.hip's tables name: 16 + 6 + 2."""
-    src = open(os.path.join(ROOT, "mfas_amd", "csrc", "mfas_hip.hip")).read()
-    body = src.split("static StepBuild step_build(")[1].split("#undef K_")[0]
-    rows = [(int(m), int(w), int(f == "true"), int(s)) for m, w, f, s in re.findall(r"K_\((\d), (\d), (true|false), (\d)\);", body)]
-    assert rows == STEP_ROWS, rows
-    body = src.split("static StepBuild same_build(")[1].split("#undef K_")[0]
-    assert [(int(m), int(s)) for m, s in re.findall(r"K_\((\d), (\d)\);", body)] == SAME_ROWS
-    assert "return !nt ? wide_sweep_of<false>() : wide_sweep_of<true>();" in src
-    assert len(ALL_BUILDS) == 24 and len(set(ALL_BUILDS)) == 24
-    assert sum(b.startswith("k_step<") for b in ALL_BUILDS) == 16 and sum(b.startswith("k_step_same<") for b in ALL_BUILDS) == 6
+    """ALL_BUILDS is what the library's sweep tables hold: 14 + 6 + 2, in the tables' order."""
+    rows = [k for k in BH.ask1("tables", None) if k.startswith(("k_step<", "k_step_same<", "k_sweep_wide<"))]
+    assert rows == ALL_BUILDS, (rows, ALL_BUILDS)
+    assert len(ALL_BUILDS) == 22 and len(set(ALL_BUILDS)) == 22
+    assert sum(b.startswith("k_step<") for b in ALL_BUILDS) == 14 and sum(b.startswith("k_step_same<") for b in ALL_BUILDS) == 6
 
 
 def test_every_reachable_build_has_a_row():
-    """The choice over every plan state reaches ALL_FORMS minus UNREACHABLE, names nothing the tables lack, and SWEEP_FORMS x
-    {cached, nontemporal} names every reachable build."""
+    """The choice over every plan state reaches ALL_FORMS minus UNREACHABLE (nothing: every build is launched by some plan), names
+    nothing the tables lack, and SWEEP_FORMS x {cached, nontemporal} names every reachable build."""
     reach = set()
     for st in plan_states():
         for over in (False, True):
             reach |= {f for f in launch_forms(st, over) if not f.startswith("k_chain")}
     assert reach <= set(ALL_FORMS), reach - set(ALL_FORMS)
     assert set(ALL_FORMS) - reach == set(UNREACHABLE), (set(ALL_FORMS) - reach, set(UNREACHABLE))
-    assert list(UNREACHABLE) == ["k_step<2,N,2,1,1>"]
+    assert list(UNREACHABLE) == []
     covered = {named(f, nt) for row in SWEEP_FORMS for f in row["forms"] if not f.startswith("k_chain") for nt in (0, 1)}
     assert covered == {named(f, nt) for f in reach for nt in (0, 1)}, covered ^ {named(f, nt) for f in reach for nt in (0, 1)}
     assert covered == set(ALL_BUILDS) - {named(f, nt) for f in UNREACHABLE for nt in (0, 1)}
@@ -287,7 +283,7 @@ def test_rows_span_the_design():
 
 @pytest.mark.parametrize("row", SWEEP_FORMS, ids=FORM_IDS)
 def test_row_record_follows_from_its_plan_facts(row):
-    """The row's expected record is what the restated choice gives for the row's plan facts, and the facts fit the row: batch tiles
+    """The row's expected record is what the header's choice gives for the row's plan facts, and the facts fit the row: batch tiles
     from B, the lean chain's and chain_split's geometry, the switches that force the schedule.  (The GPU test asserts the facts with
     pop.schedule() and the record with the library's own.)"""
     f, env = row["facts"], row["env"]
@@ -345,8 +341,8 @@ def state_bytes(R, C, widths, confs):
         24.0 * C * R * len(confs)
 
 
-NT_BYTES = 200.0 * 1024 * 1024      # plan.hip.h:730  pl.nontemporal = plane_stride * 12 > 200 MiB
-OCC_BYTES_SMALL_R = 250e6           # plan.hip.h:673  occ_bytes below eight row blocks (450e6 from R = 113 on)
+NT_BYTES = 200.0 * 1024 * 1024      # plan_layout: pl.nontemporal = plane_stride * 12 > 200 MiB
+OCC_BYTES_SMALL_R = 250e6           # plan_layout: occ_bytes below eight row blocks (450e6 from R = 113 on)
 BIG = [3, 0]                        # W_C's two widest taps: s2048 + v4100 columns per cell
 
 
@@ -395,7 +391,7 @@ def test_natural_populations_sit_at_their_thresholds():
     assert len(nt["confs"]) < 8 and state_bytes(nt["R"], nt["C"], nt["widths"], nt["confs"]) > 260e6      # one group, no same-group launch
     oc = NATURAL["natural_occ"]
     assert 17 <= oc["B"] <= 32 and len(oc["confs"]) >= 8 and -(-oc["R"] // 16) < 8
-    # plan.hip.h:551-559: the first group is the shortest prefix with half of the padded weight columns
+    # plan_layout: the first group is the shortest prefix with half of the padded weight columns
     work = [sum(GW.ceil16(oc["R"]) * (GW.ceil16(oc["widths"]["s"][c[0]]) + GW.ceil16(oc["widths"]["v"][c[1]]) + (GW.ceil16(oc["R"]) if i else 0))
                 for i, c in enumerate(conf)) + GW.ceil16(oc["C"]) * GW.ceil16(oc["R"]) for conf in oc["confs"]]
     split = next(k + 1 for k in range(len(work)) if sum(work[:k + 1]) >= sum(work) / 2)

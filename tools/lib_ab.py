@@ -41,6 +41,8 @@ SCHED_CASES = {
     "split_two_group": ("chain_split", (120, 23, 12, {"MFAS_SAME_GROUP": "0"}, 128, 8, 0, lambda s: s["groups"] == 2 and SPLIT(s)), {}),
     "split_multitask_nobn": ("chain_split", None, {"multitask": True, "bn": False}),
     "split_multilabel": ("chain_split", None, {"loss_mode": 1}),
+    # host-bound: the lean chain launch per phase (R = 16, B = 20, MFAS_PERSIST=0), one group, chain + sweep = two launches per step
+    "lean_per_phase": ("lean_chain", None, {}),
 }
 # single-candidate cases of test_gpu_ref64.CASES (general chain: more than 64 classes, alphas, multi-label, multitask, no BatchNorm)
 ENVELOPE_CASES = ("r17a", "r32a", "r33a", "r65b", "r80a", "r128a", "r128b")
