@@ -178,6 +178,15 @@ static size_t sweep_unit_lds(const Geo& g, const SegDesc& d) {
     if (nrb < STEP_NW && d.kind <= KIND_V) fl += (size_t)STEP_NW * nrb * g.MB * 256;
     return fl * 4;
 }
+// the same feature unit in a double pass (deferred stores): + the replayed step's rows and dy, which a k-split unit lays over the
+// reduction slabs of its LAST row block (sweep_body)
+static size_t sweep_unit_lds_double(const Geo& g, const SegDesc& d) {
+    const int nrb = d.rows_p / 16;
+    const size_t replay = (size_t)g.Bp * (d.cc + 16) + (size_t)g.Bp * (d.rows_p + 16), slab = (size_t)STEP_NW * g.MB * 256;
+    size_t fl = (size_t)g.Bp * (d.cc + 16) + (size_t)g.Bp * (d.cc + 4) + (size_t)g.Bp * (d.rows_p + 16);
+    fl += nrb < STEP_NW ? (size_t)(nrb - 1) * slab + std::max(slab, replay) : replay;
+    return fl * 4;
+}
 // the wide path (wide.hip.h): a sweep unit's batch slice of x_t, x_{t+1} and dy; the chain's rows in flight, logits and statistics
 static size_t wide_unit_lds(const SegDesc& d) {
     return wide_sweep_lds_floats(std::min(16 * WIDE_KB, d.cc), std::min(16 * WIDE_RBG, d.rows_p)) * 4;
@@ -329,7 +338,9 @@ struct LayoutPlan {
     int chain_split = 0;             // CUs per candidate chain in the same-group launch (0 / 1: chain_body on one CU; 4: chain_split<4>)
     bool red_in_sweep = false;       // reduce-in-sweep arrival counters [K][4] (small populations, general chain)
     bool nontemporal = false;
-    double occ_bytes = 0;            // MB == 2: group state bytes/launch above which the sweep (not the chain) bounds a fused launch
+    bool defer = false;              // feature segments store W / m / v every second step (launches.hip.h, mark_deferred)
+    int64_t sb_dy_alt = 0;           // deferring plans: the second dy area of a candidate's step buffers (Geo::sb_dy is the first)
+    double occ_bytes = 0;           // MB == 2: group state bytes/launch above which the sweep (not the chain) bounds a fused launch
     int mbe = 4, nrbw = 1;           // dev pass: batch tiles per workgroup, row blocks per wave
     bool yf_in_lds = false, vec_in_lds = false;
     size_t lds_step = 0, lds_chain = 0, lds_eval = 0;
@@ -729,6 +740,23 @@ static int plan_layout_as(const mfas_hyper* hp, const int32_t* confs, const int3
     // W/m/v beyond what the 256 MiB Infinity Cache can keep between steps are streamed nontemporally
     pl.nontemporal = (double)pl.plane_stride * 12.0 > 200.0 * 1024 * 1024;
     if (tu.nt >= 0) pl.nontemporal = tu.nt != 0;
+    // deferred stores (launches.hip.h, mark_deferred): the two-group launch-per-phase schedule with the general chain, no alphas (the
+    // replayed step would need its gradient scale too) and per-segment feature units only, where every feature unit's double pass — a plain
+    // unit's three staged tiles + the replayed step's rows and dy — fits the LDS the plan already asks for (lds_step is NOT raised for it)
+    pl.defer = pl.groups.size() == 2 && !wide && !pl.persist && !pl.same_group && !pl.lean_chain && !g.alphas;
+    for (const GroupPlan& gr : pl.groups) {
+        if (!gr.taps.empty()) pl.defer = false;
+        for (const SegDesc& d : gr.descs)
+            if (d.kind <= KIND_V && sweep_unit_lds_double(g, d) > pl.lds_step) pl.defer = false;
+    }
+    if (pl.defer) {
+        // the replayed step's dy must outlive the group's next chain: a second dy area at the END of every candidate's step-buffer block
+        // (no existing sub-offset moves); the host alternates Geo::sb_dy between the two in the per-launch arguments (train.hip.h)
+        pl.sb_dy_alt = g.sb_size;
+        g.sb_size = (g.sb_size + (int64_t)MFAS_MAX_CELLS * g.Bp * g.Rp + 63) & ~63LL;
+        for (int k = 0; k < K; ++k) pl.cands[k].step_off = (int64_t)k * g.sb_size;
+        pl.step_total = (int64_t)K * g.sb_size;
+    }
     return MFAS_OK;
 }
 

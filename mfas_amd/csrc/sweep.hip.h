@@ -1,18 +1,28 @@
 // sweep.hip.h — the HBM-bound sweep: dW + Adam + next-step forward per weight tile (per-segment and tap-major decompositions)
 // (part of the single translation unit mfas_hip.hip; see the header comment there and DESIGN.md)
 #pragma once
+#include "launches.hip.h"     // LAUNCH_PLAIN / _VIRTUAL / _DOUBLE
 // ------------------------------------------------------------------------------------------------
 // tile_run — the fused per-tile work shared by both sweep decompositions, for ONE row block `rb` over the k-blocks
 // kb0, kb0+kbs, ... < nkb of a chunk: request SWEEP_U tiles of W/m/v, then per tile
 //   dW^T = x_t^T dy (4*MB f32 MFMAs; D image == the tile image)  ->  Adam(+L2) on 4 elements/lane in registers  ->
 //   store W, m, v (+ transposed copy T for OUT/HEAD)  ->  y_{t+1} += x_{t+1} W_new^T (4*MB f32 MFMAs) into yacc.
+// Deferred stores (launches.hip.h): a virtual pass (`store` = false, wave-uniform) leaves the three stores out — the next sweep of the
+// group loads the same tiles again.  That sweep is the double pass, DBL: before its own step it replays the step left out, dW from
+// xp / dyp (the previous batch's rows in the ST layout, its dy in LDS, row stride SDp) -> Adam with that step's ss_p / bc2s_p — the same
+// instructions on the same bits, so what it stores is what two plain sweeps store.  DBL is a template argument so that the plain walk
+// keeps its registers: the caller branches once per row block, and the double walk takes both steps' dy from LDS per tile (dyc: this
+// step's, laid out like dyp) and asks for half as many tiles at a time (the full count spills in every 128-register build).
 // ------------------------------------------------------------------------------------------------
-template <int MB, bool NT, int SWEEP_U, bool COH = false>
+template <int MB, bool NT, int SWEEP_U, bool COH = false, bool DBL = false>
 __device__ __forceinline__ void tile_run(float* Wp, float* Mp, float* Vp, const int rb, const int nkb, const int kb0,
                                          const int kbs, const float* xt, const int ST, const float* xn, const int SN,
                                          const float (&dyf)[MB * 4], const float gsc, const AdamC& ac, const bool upd,
                                          const bool fwd, f32x4 (&yacc)[MB], float* T, const int tstride_rb,
-                                         const int lane, const int nj) {
+                                         const int lane, const int nj, const bool store = true, const float* xp = nullptr,
+                                         const float* dyp = nullptr, const float* dyc = nullptr, const int SDp = 0,
+                                         const float ss_p = 0.f, const float bc2s_p = 1.f) {
+    static_assert(!(DBL && COH), "the same-group launch defers nothing");
     // nj = ceil(B / 4): batch blocks that hold data (DW_BATCH_LOOP, common.hip.h)
     const int l15 = lane & 15, lg = lane >> 4;
     const float a_ss = ac.ss, a_bc2s = ac.bc2s, a_w1 = ac.w1, a_b2 = ac.b2, a_w2 = ac.w2, a_eps = ac.eps, a_wd = ac.wd;
@@ -40,15 +50,29 @@ __device__ __forceinline__ void tile_run(float* Wp, float* Mp, float* Vp, const 
             if (kb < nkb) {
                 const int64_t off = ((int64_t)rb * nkb + kb) * 256 + lane * 4;
                 if (upd) {
+                    int dq = lg * SDp + rb * 16 + l15;      // (DBL) this lane's dy column of the row block, batch row lg
+                    // (opaque per tile: as a loop invariant the 2 * MB * 4 dy values would be hoisted into registers for the whole walk)
+                    if constexpr (DBL) asm volatile("" : "+v"(dq));
+                    if constexpr (DBL) {      // the step the group's previous sweep left unstored, from the same version of the tile
+                        f32x4 accp = {0.f, 0.f, 0.f, 0.f};
+                        DW_BATCH_LOOP(MB, nj, accp = MFMA16(xp[(4 * j + lg) * ST + kb * 16 + l15], dyp[dq + 4 * j * SDp], accp))
+                        f32x4 w = w4[u], m = m4[u], v = v4[u];
+                        adam4(w, m, v, accp * gsc, ss_p, bc2s_p, a_w1, a_b2, a_w2, a_eps, a_wd);
+                        w4[u] = w; m4[u] = m; v4[u] = v;
+                        __builtin_amdgcn_sched_barrier(0);      // (this step's dW operands are not fetched under the replay: registers)
+                    }
                     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                     // (COH = the same-group fused launch: its 128-register budget has no room for two loop bodies, so it keeps the
                     // padded blocks — they add +0, which can only turn an accumulator of -0 into +0, and Adam's m, v and w come out
                     // the same for g = -0 and g = +0: tests/test_gpu_parity.py::test_same_group_launch_fuzz_bit_identical)
-                    DW_BATCH_LOOP(MB, (COH ? MB * 4 : nj), acc = MFMA16(xt[(4 * j + lg) * ST + kb * 16 + l15], dyf[j], acc))
+                    if constexpr (DBL) { DW_BATCH_LOOP(MB, nj, acc = MFMA16(xt[(4 * j + lg) * ST + kb * 16 + l15], dyc[dq + 4 * j * SDp], acc)) }
+                    else { DW_BATCH_LOOP(MB, (COH ? MB * 4 : nj), acc = MFMA16(xt[(4 * j + lg) * ST + kb * 16 + l15], dyf[j], acc)) }
                     { f32x4 w = w4[u], m = m4[u], v = v4[u];
                       adam4(w, m, v, acc * gsc, a_ss, a_bc2s, a_w1, a_b2, a_w2, a_eps, a_wd);
                       w4[u] = w; m4[u] = m; v4[u] = v; }
-                    if (NT) {
+                    if (!COH && !DBL && !store) {
+                        // (the tile goes on to the forward product and is dropped: the group's next sweep replays this step)
+                    } else if (NT) {
                         __builtin_nontemporal_store(w4[u], reinterpret_cast<f32x4*>(Wp + off));
                         __builtin_nontemporal_store(m4[u], reinterpret_cast<f32x4*>(Mp + off));
                         __builtin_nontemporal_store(v4[u], reinterpret_cast<f32x4*>(Vp + off));
@@ -118,6 +142,12 @@ struct SweepArgs {
     const char* gather;
     int64_t g_cand_stride, g_par_stride;   // bytes between two candidates' buffers / between the two parities of one
     int32_t g_par_t, g_par_n;              // parity that holds the rows of batch t / of batch t + 1
+    // deferred stores (launches.hip.h): what the feature units of this launch do with W / m / v, and for LAUNCH_DOUBLE the step they
+    // replay first: rows of batch t - 1 (table position / gathered parity), its dy area inside a candidate's step buffers, its step scalars
+    int32_t mode, g_par_p;
+    int64_t pos_p, sb_dy_prev;
+    int32_t base_p, nvalid_p;
+    float ss_p, bc2s_p;
 };
 
 // byte offset of tap (kind, tap)'s [Bp][width] block inside one parity of a candidate's gathered rows (S taps first, then V)
@@ -214,7 +244,8 @@ __device__ __forceinline__ SweepStep sweep_step_of(const SweepArgs& a) {
 #define SW_END_STAMP() do { } while (0)
 #define SW_UNIT_STAMP(k) do { } while (0)
 #endif
-template <int MB, bool NT, int U, bool COH = false>
+// (DEFER = false: a build whose plans never defer stores — the same-group launch, the lean chain's k_step — carries no double walk)
+template <int MB, bool NT, int U, bool COH = false, bool DEFER = !COH>
 __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& st, const int bid, float* lds) {
     const SegDesc d = a.desc[bid];
     const CandDev& cd = a.cands[d.cand];
@@ -228,21 +259,34 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& 
     float* xt = lds;
     float* xn = xt + Bp * ST;
     float* dyl = xn + Bp * SN;
-    float* wred = dyl + Bp * SD;   // [8 waves][nrb][MB][256], only when the chunk is k-split over waves
     const bool feat = d.kind <= KIND_V;
     const bool upd = st.upd != 0;
     const bool fwd = (st.fwd != 0) && feat;
     if (!upd && !fwd) return;
+    float* wred = dyl + Bp * SD;   // [nrb][8 waves][MB][256], only when the chunk is k-split over waves
+    // Work split: with >= 8 row blocks every wave owns whole row blocks (streams contiguous tiles, no
+    // reduction); with fewer (R < 128, or a row-split unit) the waves split the k blocks and reduce through LDS.
+    const bool split_k = nrb < STEP_NW;
+    // deferred stores: the mode of this launch's feature units (OUT / HEAD units store every step).  A double pass also stages the rows
+    // and the dy of the step it replays (xp, dyp) behind the three tiles of a plain pass; in a k-split unit over the slabs of the LAST
+    // row block, which the waves write only after a barrier behind the last tile (the host defers only where plan.hip.h's
+    // sweep_unit_lds_double fits the plan's LDS)
+    const int mode = (DEFER && feat && upd) ? a.mode : LAUNCH_PLAIN;
+    const bool dbl = mode == LAUNCH_DOUBLE;
+    float* xp = wred + (split_k ? (nrb - 1) * STEP_NW * MB * 256 : 0);
+    float* dyp = xp + Bp * ST;
     const int64_t sbo = cd.step_off;   // this candidate's step buffers inside a.stepbuf
     const bool red = a.red_cnt != nullptr;
 
     if (!COH && a.gather && feat) {      // the candidate's rows were gathered a launch ago (gather_body): rows 0 .. B-1 of its own copy
         const char* gb = a.gather + (int64_t)cd.gidx * a.g_cand_stride + gather_tap_off(a.g, d.kind, d.tap, a.tab.dtype == MFAS_DT_F32 ? 4 : 2);
+        if (dbl) stage_table(xp, ST, gb + (int64_t)a.g_par_p * a.g_par_stride, a.tab.dtype, d.width, d.k0, cc, nullptr, 0, 0, a.nvalid_p, Bp, tid, STEP_THREADS);
         if (upd) stage_table(xt, ST, gb + (int64_t)a.g_par_t * a.g_par_stride, a.tab.dtype, d.width, d.k0, cc, nullptr, 0, 0, st.nvalid_t, Bp, tid, STEP_THREADS);
         if (fwd) stage_table(xn, SN, gb + (int64_t)a.g_par_n * a.g_par_stride, a.tab.dtype, d.width, d.k0, cc, nullptr, 0, 0, st.nvalid_n, Bp, tid, STEP_THREADS);
     } else {
     if (upd && feat) {
         const void* tp = d.kind == KIND_S ? a.tab.s[d.tap] : a.tab.v[d.tap];
+        if (dbl) stage_table(xp, ST, tp, a.tab.dtype, d.width, d.k0, cc, cand_order(a.order, a.g, cd.gidx), a.pos_p, a.base_p, a.nvalid_p, Bp, tid, STEP_THREADS);
         stage_table(xt, ST, tp, a.tab.dtype, d.width, d.k0, cc, cand_order(a.order, a.g, cd.gidx), st.pos_t, st.base_t, st.nvalid_t, Bp, tid, STEP_THREADS);
     }
     if (fwd) {
@@ -283,6 +327,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& 
         // dy of this unit's rows: columns [16*rb0, 16*rb0 + rows_p) of the segment's dy (row stride = the segment's padded rows)
         const int64_t dsrc = d.kind == KIND_HEAD ? sbo + a.g.sb_dlog : sbo + a.g.sb_dy + (int64_t)d.cell * Bp * a.g.Rp;
         stage_f32<COH>(dyl, SD, a.stepbuf, dsrc + d.rb0 * 16, d.seg_nrb * 16, rows_p, Bp, tid, STEP_THREADS);
+        if (dbl) stage_f32<false>(dyp, SD, a.stepbuf, sbo + a.sb_dy_prev + (int64_t)d.cell * Bp * a.g.Rp + d.rb0 * 16, d.seg_nrb * 16, rows_p, Bp, tid, STEP_THREADS);
     }
     __syncthreads();
     SW_UNIT_STAMP(1);
@@ -296,9 +341,6 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& 
     float gsc = 1.0f;
     if (a.g.alphas && feat && upd) gsc = ldc1<COH>(a.stepbuf + sbo + a.g.sb_gsc + d.cell * 2 + d.kind);
 
-    // Work split: with >= 8 row blocks every wave owns whole row blocks (streams contiguous tiles, no
-    // reduction); with fewer (R < 128, or a row-split unit) the waves split the k blocks and reduce through LDS.
-    const bool split_k = nrb < STEP_NW;
     const int rb0 = split_k ? 0 : wave, rbs = split_k ? 1 : STEP_NW;
     const int kb0 = split_k ? wave : 0, kbs = split_k ? STEP_NW : 1;
     // partial slot of this chunk: [seg_nrb][MB][256] in MFMA D layout; this unit owns row blocks rb0 .. rb0 + nrb
@@ -306,19 +348,31 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& 
                          (((int64_t)d.rb0 * MB) << 8);
 
     for (int rb = rb0; rb < nrb; rb += rbs) {
-        float dyf[MB * 4];
-#pragma unroll
-        for (int j = 0; j < MB * 4; ++j) dyf[j] = upd ? dyl[(4 * j + lg) * SD + rb * 16 + l15] : 0.f;
+        float dyf[MB * 4];      // (the double walk reads dy from LDS tile by tile and leaves this alone)
         f32x4 yacc[MB];
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb) yacc[mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        tile_run<MB, NT, U, COH>(Wp, Mp, Vp, rb, nkb, kb0, kbs, xt, ST, xn, SN, dyf, gsc, ac, upd, fwd, yacc,
-                                 d.wt_off >= 0 ? a.wt + d.wt_off + ((int64_t)(d.k0 >> 4) * d.seg_nrb + d.rb0) * 256 : nullptr, d.seg_nrb, lane, (a.g.B + 3) >> 2);
+        float* Tt = d.wt_off >= 0 ? a.wt + d.wt_off + ((int64_t)(d.k0 >> 4) * d.seg_nrb + d.rb0) * 256 : nullptr;
+        bool plain_walk = true;
+        if constexpr (DEFER) {
+            if (dbl) {
+                plain_walk = false;
+                tile_run<MB, NT, (U > 1 ? U / 2 : 1), false, true>(Wp, Mp, Vp, rb, nkb, kb0, kbs, xt, ST, xn, SN, dyf, gsc, ac, upd, fwd, yacc, Tt, d.seg_nrb,
+                                                                    lane, (a.g.B + 3) >> 2, true, xp, dyp, dyl, SD, a.ss_p, a.bc2s_p);
+                if (split_k && fwd && rb == nrb - 1) __syncthreads();     // xp / dyp lie over the slabs this row block is about to write
+            }
+        }
+        if (plain_walk) {
+#pragma unroll
+            for (int j = 0; j < MB * 4; ++j) dyf[j] = upd ? dyl[(4 * j + lg) * SD + rb * 16 + l15] : 0.f;
+            tile_run<MB, NT, U, COH>(Wp, Mp, Vp, rb, nkb, kb0, kbs, xt, ST, xn, SN, dyf, gsc, ac, upd, fwd, yacc, Tt, d.seg_nrb, lane,
+                                     (a.g.B + 3) >> 2, mode != LAUNCH_VIRTUAL);
+        }
         if (fwd) {
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 if (split_k)
-                    *reinterpret_cast<f32x4*>(wred + (((wave * nrb + rb) * MB + mb) << 8) + lane * 4) = yacc[mb];
+                    *reinterpret_cast<f32x4*>(wred + (((rb * STEP_NW + wave) * MB + mb) << 8) + lane * 4) = yacc[mb];
                 else if (red) stc4<true>(a.stepbuf, part + ((rb * MB + mb) << 8) + lane * 4, yacc[mb]);
                 else   // partial slot in MFMA D layout [chunk][rb][mb][lane][4]
                     stc4<COH>(a.stepbuf, part + ((rb * MB + mb) << 8) + lane * 4, yacc[mb]);
@@ -332,10 +386,11 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& 
         // deterministic cross-wave reduction (fixed order 0..7)
         for (int e = tid; e < nrb * MB * 64; e += STEP_THREADS) {
             const int slot = e >> 6, ln = e & 63;
-            f32x4 s = *reinterpret_cast<const f32x4*>(wred + (slot << 8) + ln * 4);
+            const int srb = slot / MB, smb = slot - srb * MB;      // slot = rb * MB + mb of the unit's slab; wred is [rb][wave][mb]
+            f32x4 s = *reinterpret_cast<const f32x4*>(wred + (((srb * STEP_NW) * MB + smb) << 8) + ln * 4);
 #pragma unroll
             for (int w = 1; w < STEP_NW; ++w)
-                s += *reinterpret_cast<const f32x4*>(wred + ((w * nrb * MB + slot) << 8) + ln * 4);
+                s += *reinterpret_cast<const f32x4*>(wred + (((srb * STEP_NW + w) * MB + smb) << 8) + ln * 4);
             if (red) stc4<true>(a.stepbuf, part + (slot << 8) + ln * 4, s);
             else stc4<COH>(a.stepbuf, part + (slot << 8) + ln * 4, s);
         }

@@ -43,7 +43,7 @@ static hipError_t setup_gather(TrainCall& c) {
     if (!c.use_gather) return hipSuccess;
     int64_t totw = 0;
     for (int u = 0; u < MFAS_MAX_TAPS; ++u) totw += g.sw[u] + g.vw[u];
-    c.g_par_stride = totw * g.Bp * c.elt(); c.g_cand_stride = 2 * c.g_par_stride;
+    c.g_par_stride = totw * g.Bp * c.elt(); c.g_cand_stride = row_sets(p->plan.defer) * c.g_par_stride;     // (a deferring plan keeps three batches)
     const size_t need = (size_t)c.g_cand_stride * p->K;
     if (p->gather_cap < need) {
         hipFree(p->d_gather); p->d_gather = nullptr; p->gather_cap = 0;
@@ -51,7 +51,9 @@ static hipError_t setup_gather(TrainCall& c) {
         if (e != hipSuccess) { c.use_gather = false; (void)hipGetLastError(); return hipSuccess; }   // an optimisation: train without it
         p->gather_cap = need;
     }
-    if (p->tune.gather_verbose) fprintf(stderr, "[gather] on: %d candidates, %.1f MB of gathered rows\n", p->K, (double)need / 1e6);
+    if (p->tune.gather_verbose)
+        fprintf(stderr, "[gather] on: %d candidates, %.1f MB of gathered rows, %d row sets%s\n", p->K, (double)need / 1e6, row_sets(p->plan.defer),
+                p->plan.defer ? " (feature segments store W / m / v every second step)" : "");
     return hipSuccess;
 }
 
@@ -119,12 +121,13 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
         ga.buf = p->d_gather; ga.cand_stride = c.g_cand_stride; ga.par_stride = c.g_par_stride;
         for (int s = 0; s < L.gather_n; ++s) {
             const int64_t t = L.gather_b + s;
-            ga.pos[s] = ep * N + t * B; ga.base[s] = (int)(t * B); ga.nvalid[s] = nvalid(t); ga.par[s] = (int)(t & 1);
+            ga.pos[s] = ep * N + t * B; ga.base[s] = (int)(t * B); ga.nvalid[s] = nvalid(t); ga.par[s] = row_set_of(t, pl.defer);
         }
         if (L.gather_g >= 0) { ga.nsets = L.gather_n; ga.cands = p->d_cands + pl.groups[L.gather_g].c0; ga.nblocks = pl.groups[L.gather_g].nc; }
         if (gs >= 0 && L.upd) {
             st.sa.gather = p->d_gather; st.sa.g_cand_stride = c.g_cand_stride; st.sa.g_par_stride = c.g_par_stride;
-            st.sa.g_par_t = (int)(L.sweep_t & 1); st.sa.g_par_n = (int)((L.sweep_t + 1) & 1);
+            st.sa.g_par_t = row_set_of(L.sweep_t, pl.defer); st.sa.g_par_n = row_set_of(L.sweep_t + 1, pl.defer);
+            st.sa.g_par_p = row_set_of(std::max<int64_t>(L.sweep_t - 1, 0), pl.defer);
         }
     }
     if (gs >= 0) {
@@ -137,6 +140,14 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
         s.pos_n = ep * N + tn * B; s.base_n = (int)(tn * B); s.nvalid_n = nvalid(tn);
         s.ac.ss = L.upd ? c.step_scalars[2 * gstep] : 0.f;
         s.ac.bc2s = L.upd ? c.step_scalars[2 * gstep + 1] : 1.f;
+        // deferred stores: the mode, this step's dy area and — a double pass replays step ts - 1 first — that step's rows, dy area and scalars
+        s.mode = L.mode;
+        s.g.sb_dy = dy_area_of(ts, pl.defer) ? pl.sb_dy_alt : pl.g.sb_dy;
+        if (L.mode == LAUNCH_DOUBLE) {
+            s.pos_p = ep * N + (ts - 1) * B; s.base_p = (int)((ts - 1) * B); s.nvalid_p = nvalid(ts - 1);
+            s.sb_dy_prev = dy_area_of(ts - 1, pl.defer) ? pl.sb_dy_alt : pl.g.sb_dy;
+            s.ss_p = c.step_scalars[2 * (gstep - 1)]; s.bc2s_p = c.step_scalars[2 * (gstep - 1) + 1];
+        }
         nsw = (unsigned)(pl.groups[gs].descs.size() + pl.groups[gs].taps.size());
     } else st.sa.ntap = 0;
     if (gc >= 0) {
@@ -146,6 +157,7 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
         ca.pos_t = ep * N + tc * B; ca.base_t = (int)(tc * B); ca.nvalid = nvalid(tc);
         ca.gstep = (int)gstep; ca.epoch = (int)ep;
         ca.ac.ss = c.step_scalars[2 * gstep]; ca.ac.bc2s = c.step_scalars[2 * gstep + 1];
+        ca.g.sb_dy = dy_area_of(tc, pl.defer) ? pl.sb_dy_alt : pl.g.sb_dy;      // (the sweep of step tc reads it there)
         nch = (unsigned)pl.groups[gc].nc;
     }
     st.nchain = (int)nch;
@@ -154,7 +166,14 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
         return;
     }
     // algorithmic HBM bytes of this group's update+forward sweep: 24 B/param + the batch's taps + labels
-    ProfBracket prof(c, p->profiling && L.upd && L.fwd && ((c.nlaunch++ % p->prof_every) == 0),
+    // (every prof_every-th such launch, alternately that one and the one two launches on: in a deferring plan launch 16 k is always the
+    // same group's virtual pass and 16 k + 2 its double pass, so the sample weighs the short and the long kind equally)
+    bool sampled = false;
+    if (p->profiling && L.upd && L.fwd) {
+        const int64_t n = c.nlaunch++, pe = p->prof_every;
+        sampled = n % pe == (((n / pe) & 1) ? 2 % pe : 0);
+    }
+    ProfBracket prof(c, sampled,
                      pl.groups[gs].alg_state + pl.groups[gs].alg_feat * c.elt() + 8.0 * B * pl.groups[gs].nc);
     const bool same = pl.same_group && gc == gs && L.upd, split = pl.chain_split && nch > 0;     // (split in a two-group launch: no flags, the kernel boundary)
     if (split) {    // NS parts per candidate, chain blocks = NS * ceil8(candidates)
@@ -380,7 +399,11 @@ static int train_epoch(TrainCall& c, int ep, int64_t T) {
         }
     }
     if (!p->plan.persist) {
-        if (c.launches_T != T) { epoch_launches((int)p->plan.groups.size(), p->plan.same_group, T, c.use_gather, c.launches); c.launches_T = T; }
+        if (c.launches_T != T) {
+            epoch_launches((int)p->plan.groups.size(), p->plan.same_group, T, c.use_gather, c.launches);
+            if (p->plan.defer) mark_deferred((int)p->plan.groups.size(), p->plan.same_group, c.launches);
+            c.launches_T = T;
+        }
         for (const Launch& L : c.launches) launch_record(c, ep, L);
     }
     HIPCHK(hipGetLastError());
