@@ -17,7 +17,8 @@
 // Source layout (ONE translation unit; this file includes the rest): common.hip.h (device records, helpers, LDS staging), sweep.hip.h
 // (tile_run, sweep_body, sweep_tap_body), chain.hip.h (chain_body, chain_lean, softmax / BCE rows), wide.hip.h (k_chain_wide / k_sweep_wide:
 // the batch walked in tiles), eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe); host only: plan.hip.h (the switches,
-// validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated), launches.hip.h (the
+// validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated; plan_dump.hip.h: the
+// plan as text, test-hooks variant only), launches.hip.h (the
 // launches of an epoch as data), builds.hip.h (which build a launch takes, as data: the choice functions, the builds a plan can launch, the
 // tables' row lists), state.hip.h (state in and out, the candidate carry, move, the fallback), train.hip.h (the train call).  Here:
 // k_step / k_chain, the kernel tables (key -> instantiation: the only place one is named), create / destroy, the C ABI.
@@ -113,6 +114,9 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
 
 #include "builds.hip.h"
 #include "plan.hip.h"
+#ifdef MFAS_TEST_HOOKS
+#include "plan_dump.hip.h"     // mfas_test_plan_dump: the whole plan as text (tests/test_plan_cpu.py); never in the product library
+#endif
 
 // ================================================================================================
 // Host side: C ABI

@@ -2,6 +2,12 @@
 // about a population before anything is allocated.  plan_layout() is a pure function: no HIP call, no allocation on the device, the
 // CU count is an argument.  mfas_population_create lays the population out from its result, mfas_population_plan answers from it,
 // persist_fallback asks it again without the resident schedule.
+// plan_layout_as is a sequence of stages, each a function that says what it reads and writes: choose_chunk (plan_chunk; wide; the
+// resident plan that does not stand) -> layout_candidates (layout_candidate, make_seg: records, descriptors, plane / arena offsets) ->
+// lds_budgets -> dev_pass_and_streaming -> choose_schedule (enum Sched: the ONE statement of which of wide / resident / same-group / one
+// group / two groups runs) + schedule_flags -> balanced_split -> group_work_list (tap_major_units, wide_units, same_group_units,
+// row_block_unit) -> unit_dependent_flags (red_in_sweep, defer) -> resident_units_and_roles -> layout_step_buffers (once, after defer).
+// tests/test_plan_cpu.py pins the complete result (plan_dump.hip.h) for some 700 inputs.
 // (part of the single translation unit mfas_hip.hip, included after the kernels: the LDS budgets below name their constants)
 #pragma once
 // ================================================================================================
@@ -140,6 +146,16 @@ static bool batch_resident_refuses(const mfas_hyper* hp) {
     return hp->B > 64 || ((hp->C + 15) & ~15) > 8 * lpr;
 }
 
+// The S and V taps cell i of candidate k selects: true and stored (padded to 16) columns.  The one place a configuration is turned into
+// widths: plan_chunk's unit count and column total and the candidate layout read it.  (validate_inputs has bounded n_cells and the tap
+// indices before any plan is asked for: they are not masked or clamped again here.)
+struct CellWidths { int s, v, sp, vp; };
+static CellWidths cell_widths(const mfas_hyper* hp, const int32_t* confs, int k, int i) {
+    const int32_t* c = confs + (k * 4 + i) * 3;
+    const int s = hp->s_sizes[c[0]], v = hp->v_sizes[c[1]];
+    return {s, v, ceil16(s), ceil16(v)};
+}
+
 static Geo make_geo(const mfas_hyper* hp) {      // (the step-buffer offsets sb_* depend on the widest candidate: plan_layout fills them in)
     Geo g;
     memset(&g, 0, sizeof(g));
@@ -214,12 +230,61 @@ struct ChunkPlan {
     bool resident = false;           // the resident persistent schedule runs
 };
 
-static ChunkPlan plan_chunk(const mfas_hyper* hp, const Geo& g, const int32_t* confs, const int32_t* n_cells, int K, int chunk_cols,
-                            int n_cus, bool allow_persist, const Tuning& tu) {
+struct PlanIn {                      // plan_layout's arguments + which of the two kernel families is planned for
+    const mfas_hyper* hp;
+    const int32_t* confs;
+    const int32_t* n_cells;
+    const uint32_t* drop_seeds;
+    int K, chunk_cols, n_cus;
+    bool allow_persist;
+    const Tuning& tu;
+    bool wide;
+};
+
+// feature units of the population when its S / V segments are cut into chunks of <= cc_target columns, and the widest of them
+static int64_t feature_units(const PlanIn& in, int cc_target, int* max_cc) {
+    int64_t n = 0;
+    int mx = 0;
+    for (int k = 0; k < in.K; ++k)
+        for (int i = 0; i < in.n_cells[k]; ++i) {
+            const CellWidths w = cell_widths(in.hp, in.confs, k, i);
+            const int cs = pick_chunk(w.sp, cc_target), cv = pick_chunk(w.vp, cc_target);
+            n += w.sp / cs + w.vp / cv;
+            mx = std::max(mx, std::max(cs, cv));
+        }
+    if (max_cc) *max_cc = mx;
+    return n;
+}
+
+// `units` resident units of cc columns, nu per workgroup: tiles per wave, LDS, and a CU for every chain and every unit workgroup
+static bool res_units_fit(const PlanIn& in, const Geo& g, int cc, int nu, int64_t units) {
+    return (cc <= 128 * PERSIST_NTR || (in.hp->tap_bits == 16 && nu == 1 && cc <= 128 * PERSIST_NTR16)) &&
+           res_unit_lds(in.hp, g, cc, nu) <= 160 * 1024 && in.K + (units + nu - 1) / nu <= in.n_cus;
+}
+
+// The launch-per-phase chunk: a workgroup should stream >= ~64 tiles (amortises staging / reduction and keeps the number of partial-sum
+// chunks the chain has to reduce small), the launch should still have a few hundred workgroups, and x_t / x_{t+1} for the chunk must
+// fit the LDS budget.
+static int streaming_chunk(const PlanIn& in, const Geo& g) {
+    double tot_cols = 0;
+    for (int k = 0; k < in.K; ++k)
+        for (int i = 0; i < in.n_cells[k]; ++i) { const CellWidths w = cell_widths(in.hp, in.confs, k, i); tot_cols += w.sp + w.vp; }
+    int lds_max = 64;                                   // largest power of two with Bp*(2cc+20)*4 <= 72 KiB
+    while ((size_t)g.Bp * (8 * lds_max + 20) * 4 <= 72 * 1024 && lds_max < 1024) lds_max <<= 1;   // test the doubled size
+    int target = 64;
+    while (target * g.nrb < 64 * 16 && target < lds_max) target <<= 1;      // >= 64 tiles per workgroup
+    while (target > 64 && tot_cols / target < 320.0) target >>= 1;           // ... but keep >= ~320 workgroups
+    // R >= 128, measured on MI355X: 64-column chunks (finer, better-balanced workgroups) win once
+    // the chain is hidden under the other group's sweep (K >= 20); below that fewer partial chunks matter more
+    // (round 2: with reduce-in-sweep the number of partial slabs no longer loads the chain; 256-column chunks stay best up
+    // to ~28 candidates, 64 beyond — profiles/r02_popsweep_r128.log)
+    if (g.nrb >= 8) target = std::min(target, in.K >= 28 ? 64 : 256);
+    return target;
+}
+
+static ChunkPlan plan_chunk(const PlanIn& in, const Geo& g, bool allow_persist) {
+    const Tuning& tu = in.tu;
     ChunkPlan lp;
-    // A workgroup should stream >= ~64 tiles (amortises staging / reduction and keeps the number of partial-sum chunks the
-    // chain has to reduce small), the launch should still have a few hundred workgroups, and x_t / x_{t+1} for the chunk must
-    // fit the LDS budget.
     // Persistent step loop (persist.hip.h): with one row block (R <= 16) the feature units become RESIDENT (one workgroup per
     // unit, or two units per workgroup; W/m/v in registers): the column chunk is then the smallest of 128 / 256 / 512 / 1024
     // columns with which every chain and every unit workgroup gets a CU of its own.
@@ -232,24 +297,7 @@ static ChunkPlan plan_chunk(const mfas_hyper* hp, const Geo& g, const int32_t* c
     lp.lean_ok = g.nrb == 1 && g.ncb <= 4 && g.MB <= 2 && lean_chain_lds(g) <= 78 * 1024 && !tu.no_lean_chain;
     // (resident units exist only together with the resident lean chain — k_president; a population without both runs launch-per-phase)
     lp.plan_res = lp.want_persist && g.nrb == 1 && g.MB <= 2 && lp.lean_ok;
-    auto feat_units = [&](int cc_target, int* max_cc) {
-        int64_t n = 0;
-        int mx = 0;
-        for (int k = 0; k < K; ++k)
-            for (int i = 0; i < n_cells[k] && i < MFAS_MAX_CELLS; ++i) {
-                const int sw = ceil16(hp->s_sizes[confs[(k * 4 + i) * 3] & 7]), vw = ceil16(hp->v_sizes[confs[(k * 4 + i) * 3 + 1] & 7]);
-                const int cs = pick_chunk(sw, cc_target), cv = pick_chunk(vw, cc_target);
-                n += sw / cs + vw / cv;
-                mx = std::max(mx, std::max(cs, cv));
-            }
-        if (max_cc) *max_cc = mx;
-        return n;
-    };
-    auto res_fits = [&](int cc, int nu, int64_t units) {
-        return (cc <= 128 * PERSIST_NTR || (hp->tap_bits == 16 && nu == 1 && cc <= 128 * PERSIST_NTR16)) &&
-               res_unit_lds(hp, g, cc, nu) <= 160 * 1024 && K + (units + nu - 1) / nu <= n_cus;
-    };
-    lp.target = chunk_cols;
+    lp.target = in.chunk_cols;
     lp.nu = 1;
     if (lp.plan_res && lp.target <= 0) {
         // smallest units first (fewest tiles per wave on the critical path); two units per workgroup before 1024-column units
@@ -260,43 +308,23 @@ static ChunkPlan plan_chunk(const mfas_hyper* hp, const Geo& g, const int32_t* c
         const int opts[5][2] = {{256, 1}, {256, 2}, {512, 1}, {512, 2}, {1024, 1}};
         int pick = -1;
         for (int o = 0; o < 5 && pick < 0; ++o)
-            if (res_fits(opts[o][0], opts[o][1], feat_units(opts[o][0], nullptr))) pick = o;
+            if (res_units_fit(in, g, opts[o][0], opts[o][1], feature_units(in, opts[o][0], nullptr))) pick = o;
         if (pick >= 0) { lp.target = opts[pick][0]; lp.nu = opts[pick][1]; }
         else lp.plan_res = false;
     } else if (lp.plan_res) {
-        const int64_t units = feat_units(lp.target, nullptr);
-        if (res_fits(lp.target, 1, units)) lp.nu = 1;
-        else if (res_fits(lp.target, 2, units)) lp.nu = 2;
+        const int64_t units = feature_units(in, lp.target, nullptr);
+        if (res_units_fit(in, g, lp.target, 1, units)) lp.nu = 1;
+        else if (res_units_fit(in, g, lp.target, 2, units)) lp.nu = 2;
         else lp.plan_res = false;
     }
-    if (lp.target <= 0) {
-        double tot_cols = 0;
-        for (int k = 0; k < K; ++k)
-            for (int i = 0; i < n_cells[k] && i < MFAS_MAX_CELLS; ++i)
-                tot_cols += ceil16(hp->s_sizes[confs[(k * 4 + i) * 3] & 7]) + ceil16(hp->v_sizes[confs[(k * 4 + i) * 3 + 1] & 7]);
-        int lds_max = 64;                                   // largest power of two with Bp*(2cc+20)*4 <= 72 KiB
-        while ((size_t)g.Bp * (8 * lds_max + 20) * 4 <= 72 * 1024 && lds_max < 1024) lds_max <<= 1;   // test the doubled size
-        int target = 64;
-        while (target * g.nrb < 64 * 16 && target < lds_max) target <<= 1;      // >= 64 tiles per workgroup
-        while (target > 64 && tot_cols / target < 320.0) target >>= 1;           // ... but keep >= ~320 workgroups
-        // R >= 128, measured on MI355X: 64-column chunks (finer, better-balanced workgroups) win once
-        // the chain is hidden under the other group's sweep (K >= 20); below that fewer partial chunks matter more
-        // (round 2: with reduce-in-sweep the number of partial slabs no longer loads the chain; 256-column chunks stay best up
-        // to ~28 candidates, 64 beyond — profiles/r02_popsweep_r128.log)
-        if (g.nrb >= 8) target = std::min(target, K >= 28 ? 64 : 256);
-        lp.target = target;
-    }
+    if (lp.target <= 0) lp.target = streaming_chunk(in, g);
     lp.target = std::max(16, (lp.target / 16) * 16);
-    {
-        int mx = 0;
-        lp.nfeat = (int)feat_units(lp.target, &mx);
-        lp.max_fcc = mx;
-    }
-    lp.res_ok = lp.plan_res && res_fits(lp.max_fcc, lp.nu, lp.nfeat);
+    lp.nfeat = (int)feature_units(in, lp.target, &lp.max_fcc);
+    lp.res_ok = lp.plan_res && res_units_fit(in, g, lp.max_fcc, lp.nu, lp.nfeat);
     lp.res_wide = lp.res_ok && lp.max_fcc > 128 * PERSIST_NTR;      // 16-bit staging only
     lp.nres_wg = lp.res_ok ? (lp.nfeat + lp.nu - 1) / lp.nu : 0;
     // persistent step loop: small populations (one workgroup per CU must hold every chain + a useful number of sweep workgroups)
-    lp.resident = lp.want_persist && lp.res_ok && K <= n_cus / 4 && g.MB != 4 && K + lp.nres_wg <= n_cus;
+    lp.resident = lp.want_persist && lp.res_ok && in.K <= in.n_cus / 4 && g.MB != 4 && in.K + lp.nres_wg <= in.n_cus;
     return lp;
 }
 
@@ -354,171 +382,167 @@ struct LayoutPlan {
     std::vector<int32_t> role;       // [K + nres_wg] role of every workgroup of the resident launch (XCD-aware placement); empty: block b runs role b
 };
 
-static int plan_layout_as(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int K, int chunk_cols,
-                          int n_cus, bool allow_persist, const Tuning& tu, const bool wide, LayoutPlan& pl) {
-    pl = LayoutPlan();
-    pl.wide = wide;
-    Geo& g = pl.g;
-    g = make_geo(hp);
-    const int vec_size = (g.vec_head + g.Cp + 63) & ~63;
-
-    // ---- column chunk per workgroup and the schedule
+// ---- the stages of plan_layout_as, in the order they run: each reads the inputs (PlanIn) and what earlier stages wrote into the plan
+// Stage 1, the column chunk.  reads: the inputs, Geo.  returns: the chunk and, for the batch-resident kernels, whether the resident
+// schedule stands (plan_chunk).
+static ChunkPlan choose_chunk(const PlanIn& in, const Geo& g) {
     ChunkPlan lp;
-    if (wide) {      // feature chunks of <= 8 k-blocks: one wide unit keeps a chunk's dW tiles of its row block in registers
-        lp.target = chunk_cols > 0 ? std::min(16 * WIDE_KB, chunk_cols) : 16 * WIDE_KB;
+    if (in.wide) {   // feature chunks of <= 8 k-blocks: one wide unit keeps a chunk's dW tiles of its row block in registers
+        lp.target = in.chunk_cols > 0 ? std::min(16 * WIDE_KB, in.chunk_cols) : 16 * WIDE_KB;
         lp.target = std::max(16, (lp.target / 16) * 16);
-    } else {
-        lp = plan_chunk(hp, g, confs, n_cells, K, chunk_cols, n_cus, allow_persist, tu);
-        if (lp.res_ok && !lp.resident)    // units were chosen for the resident schedule, which does not stand: the launch-per-phase chunking
-            lp = plan_chunk(hp, g, confs, n_cells, K, chunk_cols, n_cus, false, tu);
+        return lp;
     }
-    const int target = pl.chunk = lp.target;
+    lp = plan_chunk(in, g, in.allow_persist);
+    if (lp.res_ok && !lp.resident)    // units were chosen for the resident schedule, which does not stand: the launch-per-phase chunking
+        lp = plan_chunk(in, g, false);
+    return lp;
+}
+
+// The descriptor of a whole weight matrix segment — a cell's S, V or OUT columns (rows = R) or the head (rows = C) — with everything its
+// chunks share; the caller cuts it: tap, k0, cc, w_off, wt_off, part_idx.
+static SegDesc make_seg(int cand, int kind, int cell, int rows, int rows_p, int cols, int width, int64_t src_off, int src_ld, int src_col0,
+                        uint32_t init_seed, int fan_in) {
+    SegDesc d;
+    memset(&d, 0, sizeof(d));
+    d.cand = cand; d.kind = kind; d.cell = cell;
+    d.rows = rows; d.rows_p = rows_p; d.cols = cols; d.width = width;
+    d.src_off = src_off; d.src_ld = src_ld; d.src_col0 = src_col0;
+    d.init_seed = init_seed; d.init_bound = (float)(1.0 / sqrt((double)fan_in));
+    d.rb0 = 0; d.seg_nrb = rows_p / 16;
+    return d;
+}
+
+struct LayoutCursor {                // where the next candidate goes
+    int64_t plane = 0, wt = 0;       // floats into a W / m / v plane, into the transposed arena
+    double alg_bytes = 0, alg_feat = 0;
+};
+
+// One candidate at the cursor: its record (flat-parameter offsets in state_dict order, plane and arena offsets, chunk counts) and its
+// descriptors — per cell the S and V chunks of `pl.chunk` columns and, from the second cell on, OUT; then the head.
+// reads: the inputs, Geo, pl.chunk.  writes: pl.cands[k], pl.nparams[k], appends to pl.descs, moves the cursor.  returns: the
+// candidate's partial slots (one per feature chunk).
+static int layout_candidate(const PlanIn& in, int k, LayoutCursor& cur, LayoutPlan& pl) {
+    const mfas_hyper* hp = in.hp;
+    const Geo& g = pl.g;
+    CandDev& c = pl.cands[k];
+    memset(&c, 0, sizeof(c));
+    const int L = c.L = in.n_cells[k];
+    c.drop_seed = in.drop_seeds ? in.drop_seeds[k] : (uint32_t)k;
+    c.gidx = k;
+    c.vec_off = cur.plane;
+    cur.plane += (g.vec_head + g.Cp + 63) & ~63;
+    int64_t f = 0;
+    c.f_alpha = f; f += L;
+    int pslot = 0;
+    for (int i = 0; i < L; ++i) {
+        for (int j = 0; j < 3; ++j) { c.conf[i][j] = in.confs[(k * 4 + i) * 3 + j]; c.seg_off[i][j] = -1; }
+        const CellWidths w = cell_widths(hp, in.confs, k, i);
+        const int Kin = c.K_in[i] = w.s + w.v + (i > 0 ? hp->R : 0);
+        c.f_W[i] = f; f += (int64_t)hp->R * Kin;
+        c.f_b[i] = f; f += hp->R;
+        c.f_bn[i] = f; if (hp->bn) f += 4 * (int64_t)hp->R;
+        c.part_cell_off[i] = pslot;
+        const int widths[3] = {w.sp, w.vp, g.Rp};        // stored (padded) columns = table row stride
+        const int true_w[3] = {w.s, w.v, hp->R};         // reference columns
+        const int col0[3] = {0, w.s, w.s + w.v};
+        for (int j = 0; j < (i == 0 ? 2 : 3); ++j) {     // (the first cell has no OUT segment)
+            const int cols_p = widths[j], cc = j < 2 ? pick_chunk(cols_p, pl.chunk) : cols_p, nch = cols_p / cc;
+            c.seg_off[i][j] = cur.plane; c.seg_cc[i][j] = cc; c.seg_cols[i][j] = cols_p;
+            if (j == 0) c.nch_s[i] = nch;
+            if (j == 1) c.nch_v[i] = nch;
+            if (j == 2) c.outT_off[i] = cur.wt;
+            SegDesc d = make_seg(k, j, i, hp->R, g.Rp, true_w[j], cols_p, c.f_W[i], Kin, col0[j], 2 * i, Kin);
+            d.tap = j < 2 ? c.conf[i][j] : 0; d.cc = cc; d.wt_off = j == 2 ? cur.wt : -1;
+            for (int ch = 0; ch < nch; ++ch) {
+                d.k0 = ch * cc; d.w_off = cur.plane + (int64_t)ch * g.Rp * cc;
+                d.part_idx = j == 0 ? ch : (j == 1 ? c.nch_s[i] + ch : 0);      // one partial slab per chunk
+                pl.descs.push_back(d);
+            }
+            if (j < 2) pslot += nch;
+            cur.plane += (int64_t)g.Rp * cols_p;
+            if (j == 2) cur.wt += (int64_t)g.Rp * g.Rp;
+            cur.alg_bytes += 24.0 * hp->R * true_w[j];
+            if (j < 2) cur.alg_feat += (double)hp->B * true_w[j];   // x elements (dtype size applied at train time)
+        }
+    }
+    c.f_Wc = f; f += (int64_t)hp->C * hp->R;
+    c.f_bc = f; f += hp->C;
+    pl.nparams[k] = f;
+    c.head_off = cur.plane;
+    c.headT_off = cur.wt;
+    SegDesc d = make_seg(k, KIND_HEAD, L - 1, hp->C, g.Cp, hp->R, g.Rp, c.f_Wc, hp->R, 0, 10, hp->R);
+    d.cc = g.Rp; d.w_off = cur.plane; d.wt_off = cur.wt;
+    pl.descs.push_back(d);
+    cur.plane += (int64_t)g.Cp * g.Rp;
+    cur.wt += (int64_t)g.Cp * g.Rp;
+    cur.alg_bytes += 24.0 * hp->C * hp->R;
+    cur.plane = (cur.plane + 63) & ~63LL;
+    return pslot;
+}
+
+// Stage 2, the candidate layout.  reads: the inputs, Geo, pl.chunk.  writes: cands (all but step_off), descs, desc_start, nparams,
+// cand_plane_base / _size, plane_stride, wt_size, bytes_per_launch.  returns: the partial slots of the widest candidate.
+static int layout_candidates(const PlanIn& in, LayoutPlan& pl) {
+    const int K = in.K;
     pl.cands.resize(K);
     pl.desc_start.assign(K + 1, 0);
     pl.nparams.resize(K);
     pl.cand_plane_base.resize(K);
     pl.cand_plane_size.resize(K);
-    int64_t plane_off = 0, wt_off = 0, step_off = 0;
-    double alg_bytes = 0.0, alg_feat = 0.0;
+    LayoutCursor cur;
     int max_slots = 0;
-    std::vector<int> slots(K);
-    // first pass: layout
     for (int k = 0; k < K; ++k) {
-        CandDev& c = pl.cands[k];
-        memset(&c, 0, sizeof(c));
-        const int L = n_cells[k];
-        c.L = L;
-        c.drop_seed = drop_seeds ? drop_seeds[k] : (uint32_t)k;
-        c.gidx = k;
         pl.desc_start[k] = (int)pl.descs.size();
-        pl.cand_plane_base[k] = plane_off;
-        c.vec_off = plane_off;
-        plane_off += vec_size;
-        int64_t f = 0;
-        c.f_alpha = f; f += L;
-        int pslot = 0;
-        for (int i = 0; i < L; ++i) {
-            for (int j = 0; j < 3; ++j) {
-                c.conf[i][j] = confs[(k * 4 + i) * 3 + j];
-                c.seg_off[i][j] = -1;
-            }
-            const int sw = hp->s_sizes[c.conf[i][0]], vw = hp->v_sizes[c.conf[i][1]];
-            const int Kin = sw + vw + (i > 0 ? hp->R : 0);
-            c.K_in[i] = Kin;
-            c.f_W[i] = f; f += (int64_t)hp->R * Kin;
-            c.f_b[i] = f; f += hp->R;
-            c.f_bn[i] = f; if (hp->bn) f += 4 * (int64_t)hp->R;
-            c.part_cell_off[i] = pslot;
-            const float bound = (float)(1.0 / sqrt((double)Kin));
-            const int widths[3] = {ceil16(sw), ceil16(vw), g.Rp};     // stored (padded) columns = table row stride
-            const int true_w[3] = {sw, vw, hp->R};                     // reference columns
-            const int col0[3] = {0, sw, sw + vw};
-            for (int j = 0; j < 3; ++j) {
-                if (j == 2 && i == 0) continue;
-                const int cols_p = widths[j];
-                const int cc = j < 2 ? pick_chunk(cols_p, target) : cols_p;
-                const int nch = cols_p / cc;
-                c.seg_off[i][j] = plane_off;
-                c.seg_cc[i][j] = cc;
-                c.seg_cols[i][j] = cols_p;
-                if (j == 0) c.nch_s[i] = nch;
-                if (j == 1) c.nch_v[i] = nch;
-                if (j == 2) { c.outT_off[i] = wt_off; }
-                for (int ch = 0; ch < nch; ++ch) {
-                    SegDesc d;
-                    memset(&d, 0, sizeof(d));
-                    d.cand = k; d.kind = j; d.cell = i; d.tap = j < 2 ? c.conf[i][j] : 0;
-                    d.k0 = ch * cc; d.cc = cc; d.rows_p = g.Rp; d.width = j < 2 ? widths[j] : g.Rp;
-                    d.w_off = plane_off + (int64_t)ch * g.Rp * cc;
-                    d.wt_off = j == 2 ? wt_off : -1;
-                    d.part_idx = j < 2 ? (j == 0 ? ch : c.nch_s[i] + ch) : 0;     // one partial slab per chunk
-                    d.rows = hp->R; d.cols = true_w[j];
-                    d.src_off = c.f_W[i]; d.src_ld = Kin; d.src_col0 = col0[j];
-                    d.init_seed = 2 * i; d.init_bound = bound;
-                    d.rb0 = 0; d.seg_nrb = g.nrb;
-                    pl.descs.push_back(d);
-                }
-                if (j < 2) pslot += nch;
-                plane_off += (int64_t)g.Rp * cols_p;
-                if (j == 2) wt_off += (int64_t)g.Rp * g.Rp;
-                alg_bytes += 24.0 * hp->R * true_w[j];
-                if (j < 2) alg_feat += (double)hp->B * true_w[j];   // x elements (dtype size applied at train time)
-            }
-        }
-        c.f_Wc = f; f += (int64_t)hp->C * hp->R;
-        c.f_bc = f; f += hp->C;
-        pl.nparams[k] = f;
-        {   // head
-            c.head_off = plane_off;
-            c.headT_off = wt_off;
-            SegDesc d;
-            memset(&d, 0, sizeof(d));
-            d.cand = k; d.kind = KIND_HEAD; d.cell = L - 1; d.tap = 0;
-            d.k0 = 0; d.cc = g.Rp; d.rows_p = g.Cp; d.width = g.Rp;
-            d.w_off = plane_off; d.wt_off = wt_off; d.part_idx = 0;
-            d.rows = hp->C; d.cols = hp->R;
-            d.src_off = c.f_Wc; d.src_ld = hp->R; d.src_col0 = 0;
-            d.init_seed = 10; d.init_bound = (float)(1.0 / sqrt((double)hp->R));
-            d.rb0 = 0; d.seg_nrb = g.ncb;
-            pl.descs.push_back(d);
-            plane_off += (int64_t)g.Cp * g.Rp;
-            wt_off += (int64_t)g.Cp * g.Rp;
-            alg_bytes += 24.0 * hp->C * hp->R;
-        }
-        plane_off = (plane_off + 63) & ~63LL;
-        pl.cand_plane_size[k] = plane_off - pl.cand_plane_base[k];
-        slots[k] = pslot;
-        max_slots = std::max(max_slots, pslot);
+        pl.cand_plane_base[k] = cur.plane;
+        max_slots = std::max(max_slots, layout_candidate(in, k, cur, pl));
+        pl.cand_plane_size[k] = cur.plane - pl.cand_plane_base[k];
     }
     pl.desc_start[K] = (int)pl.descs.size();
-    // step buffers (same geometry for every candidate: sized for the largest)
-    {
-        const int64_t br = (int64_t)g.Bp * g.Rp;
-        int64_t o = 0;
-        g.sb_part = o; o += (int64_t)max_slots * br;
-        g.sb_dy = o; o += MFAS_MAX_CELLS * br;
-        g.sb_xo = o; o += MFAS_MAX_CELLS * br;
-        g.sb_dlog = o; o += (int64_t)g.Bp * g.Cp;
-        g.sb_sav = o; o += 3 * MFAS_MAX_CELLS * br;
-        g.sb_yf = o; o += 2 * MFAS_MAX_CELLS * br;
-        g.sb_gsc = o; o += 16;
-        g.sb_size = (o + 63) & ~63LL;
-        for (int k = 0; k < K; ++k) { pl.cands[k].step_off = step_off; step_off += g.sb_size; }
-    }
-    pl.plane_stride = plane_off;
-    pl.wt_size = wt_off;
-    pl.step_total = step_off;
-    pl.bytes_per_launch = alg_bytes + 4.0 * alg_feat;
+    pl.plane_stride = cur.plane;
+    pl.wt_size = cur.wt;
+    pl.bytes_per_launch = cur.alg_bytes + 4.0 * cur.alg_feat;
+    return max_slots;
+}
 
-    // ---- LDS budgets
-    if (wide) {
+// Stage 3, the LDS budgets of the training kernels.  reads: Geo, descs, the chunk plan.  writes: lds_step, lds_chain, lds_president,
+// yf_in_lds, vec_in_lds, lean_chain and — taken over from the chunk plan — persist, res_chain, res_wide, nres, res_nu, nres_wg,
+// res_buf_words.  (The wide plan has none of the resident facts: they keep their defaults.)
+static void lds_budgets(const PlanIn& in, const ChunkPlan& lp, LayoutPlan& pl) {
+    const Geo& g = pl.g;
+    if (in.wide) {
         for (const SegDesc& d : pl.descs) pl.lds_step = std::max(pl.lds_step, wide_unit_lds(d));
         pl.lds_chain = wide_chain_lds(g);
-    } else {
-        // resident feature units (persistent schedule) do not go through sweep_body: their LDS need is separate
-        pl.persist = lp.resident;
-        pl.res_chain = lp.res_ok;
-        pl.res_wide = lp.res_wide;
-        pl.nres = lp.res_ok ? lp.nfeat : 0;
-        pl.res_nu = lp.nu;
-        pl.nres_wg = lp.nres_wg;
-        pl.res_buf_words = (int)(res_batch_lds(hp, g, lp.max_fcc) / 4);
-        size_t ls = 0;
-        for (const SegDesc& d : pl.descs)
-            if (!(lp.res_ok && d.kind <= KIND_V)) ls = std::max(ls, sweep_unit_lds(g, d));
-        // chain: ping-pong activations + logits + misc (+ reduced feature sums when they fit next to the sweep's need)
-        const size_t base = ((size_t)2 * g.Bp * (g.Rp + 4) + (size_t)g.Bp * (g.Cp + 4) + MFAS_MAX_CELLS * g.Rp + 3 * g.Bp + 16) * 4;
-        const size_t yf = (size_t)(g.alphas ? 2 : 1) * MFAS_MAX_CELLS * g.nrb * g.MB * 256 * 4;
-        pl.yf_in_lds = base + yf <= std::max<size_t>(ls, 64 * 1024);
-        pl.lds_step = std::max(ls, base + (pl.yf_in_lds ? yf : 0));
-        const size_t vec = vec_lds(g);
-        pl.vec_in_lds = base + (pl.yf_in_lds ? yf : 0) + vec <= 150 * 1024;
-        pl.lds_chain = base + (pl.yf_in_lds ? yf : 0) + (pl.vec_in_lds ? vec : 0);
-        pl.lean_chain = lp.lean_ok;
-        if (pl.lean_chain) { pl.lds_chain = lean_chain_lds(g); pl.lds_step = std::max(pl.lds_step, pl.lds_chain); }
-        const size_t lds_rchain = pl.res_chain ? pl.lds_chain + 16 + 4 * (size_t)(LeanLds<1>::own_floats() - LeanLds<1>::stage_floats()) : 0;
-        pl.lds_president = ((std::max(lds_rchain, res_unit_lds(hp, g, lp.max_fcc, lp.nu)) + 15) & ~(size_t)15) + 4 * PERSIST_LDS_WORDS;
+        return;
     }
+    // resident feature units (persistent schedule) do not go through sweep_body: their LDS need is separate
+    pl.persist = lp.resident;
+    pl.res_chain = lp.res_ok;
+    pl.res_wide = lp.res_wide;
+    pl.nres = lp.res_ok ? lp.nfeat : 0;
+    pl.res_nu = lp.nu;
+    pl.nres_wg = lp.nres_wg;
+    pl.res_buf_words = (int)(res_batch_lds(in.hp, g, lp.max_fcc) / 4);
+    size_t ls = 0;
+    for (const SegDesc& d : pl.descs)
+        if (!(lp.res_ok && d.kind <= KIND_V)) ls = std::max(ls, sweep_unit_lds(g, d));
+    // chain: ping-pong activations + logits + misc (+ reduced feature sums when they fit next to the sweep's need)
+    const size_t base = ((size_t)2 * g.Bp * (g.Rp + 4) + (size_t)g.Bp * (g.Cp + 4) + MFAS_MAX_CELLS * g.Rp + 3 * g.Bp + 16) * 4;
+    const size_t yf = (size_t)(g.alphas ? 2 : 1) * MFAS_MAX_CELLS * g.nrb * g.MB * 256 * 4;
+    pl.yf_in_lds = base + yf <= std::max<size_t>(ls, 64 * 1024);
+    pl.lds_step = std::max(ls, base + (pl.yf_in_lds ? yf : 0));
+    const size_t vec = vec_lds(g);
+    pl.vec_in_lds = base + (pl.yf_in_lds ? yf : 0) + vec <= 150 * 1024;
+    pl.lds_chain = base + (pl.yf_in_lds ? yf : 0) + (pl.vec_in_lds ? vec : 0);
+    pl.lean_chain = lp.lean_ok;
+    if (pl.lean_chain) { pl.lds_chain = lean_chain_lds(g); pl.lds_step = std::max(pl.lds_step, pl.lds_chain); }
+    const size_t lds_rchain = pl.res_chain ? pl.lds_chain + 16 + 4 * (size_t)(LeanLds<1>::own_floats() - LeanLds<1>::stage_floats()) : 0;
+    pl.lds_president = ((std::max(lds_rchain, res_unit_lds(in.hp, g, lp.max_fcc, lp.nu)) + 15) & ~(size_t)15) + 4 * PERSIST_LDS_WORDS;
+}
+
+// Stage 4, the dev pass and what streams.  reads: Geo, lds_step, lds_chain, plane_stride.  writes: nrbw, mbe, lds_eval, fits_lds, occ_bytes,
+// nontemporal.
+static void dev_pass_and_streaming(const PlanIn& in, LayoutPlan& pl) {
+    const Geo& g = pl.g;
     // dev-pass row blocks per wave: k_eval is built for 1, 2, 4 and 8 (eval.hip.h clamps / skips row blocks >= nrb), so 3 and
     // 5..7 (R = 257..448) take the next build up
     pl.nrbw = (g.nrb + 3) / 4;
@@ -529,234 +553,307 @@ static int plan_layout_as(const mfas_hyper* hp, const int32_t* confs, const int3
         pl.lds_eval = ((size_t)ME * std::max(EVAL_CE + 8, g.Cp + 4) + (size_t)ME * (g.Rp + 8)) * 4;   // strides: eval.hip.h
         if (pl.lds_eval <= 80 * 1024) break;
     }
-    pl.fits_lds = !(pl.mbe < 1 || pl.nrbw > 8 || pl.lds_step > 150 * 1024 || (wide && pl.lds_chain > 150 * 1024));     // (create refuses what does not fit; the plan query still answers)
+    // (create refuses what does not fit; the plan query still answers)
+    pl.fits_lds = !(pl.mbe < 1 || pl.nrbw > 8 || pl.lds_step > 150 * 1024 || (in.wide && pl.lds_chain > 150 * 1024));
+    // measured crossover (MI355X, B=20): R=16 between 165 and 330 MB of group state per launch, R=128 between 300 and 600 MB
+    // (the spilling chain of the occupancy build takes ~40 / ~125 us there)
+    pl.occ_bytes = g.nrb >= 8 ? 450e6 : 250e6;
+    if (in.tu.occ_bytes >= 0) pl.occ_bytes = in.tu.occ_bytes;
+    // W/m/v beyond what the 256 MiB Infinity Cache can keep between steps are streamed nontemporally
+    pl.nontemporal = (double)pl.plane_stride * 12.0 > 200.0 * 1024 * 1024;
+    if (in.tu.nt >= 0) pl.nontemporal = in.tu.nt != 0;
+}
 
-    {   // candidate groups: two halves balanced by work (descriptor columns), contiguous ranges
-        // Two groups (the chain of one runs under the sweep of the other).  Measured on MI355X (cand/s, unfused vs fused):
-        // general chain, R=128: 16 candidates 104 vs 96, 20: 103 vs 110, 32: 119 vs 142 -> fused from 20;
-        // lean chain, R=16 (18 us, cheap enough to run as its own launch over all CUs): 32: 348 vs 307, 40: 361 vs 364,
-        // 50: 430 vs 475, 100: 582 vs 677, 200: 566 vs 600, 256: 630 vs 619, 512: 685 vs 641 -> fused only for 40 <= K < 224.
-        // round 2, general chain with reduce-in-sweep (chain 48 -> 38 us at R=128): fused from 8 candidates
-        // (R=128 cand/s unfused+reduce vs fused+reduce: 12 candidates 18.1 vs 20.2, 16: 21.0 vs 23.6, 24: 22.9 (old default) vs 26.6)
-        int ngroups = pl.lean_chain ? ((K >= 40 && K < 224) ? 2 : 1) : (K >= 8 ? 2 : 1);
-        if (tu.groups > 0) ngroups = (tu.groups >= 2 && K >= 2) ? 2 : 1;
-        if (pl.persist || wide) ngroups = 1;
-        // same-group fused launch (k_step_same): general chain, one group, R >= 128 (no tap-major units), launch-per-phase
-        {
-            const int sgenv = tu.same_group;     // 0: never, 2: whatever the size (A/B runs)
-            // measured (MI355X, conf 4, B=16): pays while the population's W/m/v stream is <= ~260 MB per step — R=128: 1 / 3 / 6 / 8 / 12
-            // candidates 56 / 65 / 76 / 81 / 91 -> 50 / 54 / 63 / 70 / 88 us per step (16: equal); R=64: 6 / 12 / 16: 52 / 61 / 64 -> 45 / 55 / 61
-            // (24: 74 -> 79); R=32: 6 / 12 / 32: 45 / 54 / 68 -> 36 / 41 / 60 (64: 85 -> 90)
-            double state_bytes = 0;
-            for (const SegDesc& d : pl.descs) state_bytes += 24.0 * d.cc * d.rows_p;
-            const bool two_forced = tu.groups >= 2;      // (tests: the two-group fused schedule)
-            pl.same_group = !wide && !pl.persist && !pl.lean_chain && g.MB <= 2 && (state_bytes <= 260e6 || sgenv == 2) && sgenv != 0 && !two_forced;
+// Which of its five schedules a population trains under.  They exclude each other, and the LayoutPlan flags the consumers read
+// (wide, persist, same_group, groups.size(), chain_split, red_in_sweep, defer, tap-major units) all follow from this one choice.
+enum class Sched {
+    Wide,        // wide.hip.h, launch per phase, one group: exactly the geometries the batch-resident kernels refuse
+    Resident,    // k_president: one launch per epoch
+    SameGroup,   // k_step_same: one launch per step, chain and sweep blocks of the same candidates
+    OneGroup,    // launch per phase: chain, then sweep
+    TwoGroups,   // launch per phase, fused: the chain of one group runs under the sweep of the other
+};
+static bool launch_per_phase(Sched s) { return s == Sched::OneGroup || s == Sched::TwoGroups; }
+
+// Stage 5, the schedule.  reads: the inputs, Geo, descs, persist, lean_chain.
+static Sched choose_schedule(const PlanIn& in, const LayoutPlan& pl) {
+    const Tuning& tu = in.tu;
+    const int K = in.K;
+    if (in.wide) return Sched::Wide;
+    if (pl.persist) return Sched::Resident;
+    // same-group fused launch (k_step_same): general chain, launch-per-phase.  MFAS_SAME_GROUP = 0: never, 2: whatever the size (A/B runs);
+    // MFAS_GROUPS=2 (tests: the two-group fused schedule) goes before it.
+    // measured (MI355X, conf 4, B=16): pays while the population's W/m/v stream is <= ~260 MB per step — R=128: 1 / 3 / 6 / 8 / 12
+    // candidates 56 / 65 / 76 / 81 / 91 -> 50 / 54 / 63 / 70 / 88 us per step (16: equal); R=64: 6 / 12 / 16: 52 / 61 / 64 -> 45 / 55 / 61
+    // (24: 74 -> 79); R=32: 6 / 12 / 32: 45 / 54 / 68 -> 36 / 41 / 60 (64: 85 -> 90)
+    double state_bytes = 0;
+    for (const SegDesc& d : pl.descs) state_bytes += 24.0 * d.cc * d.rows_p;
+    if (!pl.lean_chain && pl.g.MB <= 2 && (state_bytes <= 260e6 || tu.same_group == 2) && tu.same_group != 0 && tu.groups < 2) return Sched::SameGroup;
+    // Two groups (the chain of one runs under the sweep of the other).  Measured on MI355X (cand/s, unfused vs fused):
+    // general chain, R=128: 16 candidates 104 vs 96, 20: 103 vs 110, 32: 119 vs 142 -> fused from 20;
+    // lean chain, R=16 (18 us, cheap enough to run as its own launch over all CUs): 32: 348 vs 307, 40: 361 vs 364,
+    // 50: 430 vs 475, 100: 582 vs 677, 200: 566 vs 600, 256: 630 vs 619, 512: 685 vs 641 -> fused only for 40 <= K < 224.
+    // round 2, general chain with reduce-in-sweep (chain 48 -> 38 us at R=128): fused from 8 candidates
+    // (R=128 cand/s unfused+reduce vs fused+reduce: 12 candidates 18.1 vs 20.2, 16: 21.0 vs 23.6, 24: 22.9 (old default) vs 26.6)
+    bool two = pl.lean_chain ? (K >= 40 && K < 224) : K >= 8;
+    if (tu.groups > 0) two = tu.groups >= 2 && K >= 2;
+    return two ? Sched::TwoGroups : Sched::OneGroup;
+}
+
+// What follows from the schedule before the work lists are built.  writes: same_group, chain_split, lds_split.
+static int schedule_flags(const PlanIn& in, Sched s, LayoutPlan& pl) {
+    const Geo& g = pl.g;
+    pl.same_group = s == Sched::SameGroup;
+    // the chain of one candidate over 4 CUs (chain.hip.h, chain_split): eight row blocks, one batch tile, <= 4 class blocks, no alphas
+    // — in the same-group launch, and in the two-group launches while the chain bounds them (< 28 candidates: sweep(8 candidates) = 36 us
+    // against a 47 us chain; beyond, the chain hides under the other group's sweep and 4 x 64 chain workgroups would only take CUs from it)
+    pl.chain_split = ((s == Sched::SameGroup || (s == Sched::TwoGroups && in.K < 28)) && !pl.lean_chain && g.MB == 1 && g.nrb == 8 && g.ncb <= 4 &&
+                      !g.alphas && in.tu.chain_split != 0 && in.tu.chain_split != 1) ? 4 : 0;
+    if (pl.chain_split) {
+        pl.lds_split = std::max(pl.lds_step, chain_split_lds_floats<4>(g.Rp, g.Cp) * 4);
+        if ((size_t)in.K * XCH_CAND_FLOATS >= (1ull << 30)) return fail(MFAS_EINVAL, "internal: exchange area beyond the 32-bit buffer offsets");
+    }
+    return MFAS_OK;
+}
+
+// Stage 6, the balanced group split of the two-group schedule: contiguous halves balanced by work (descriptor columns).
+// reads: descs, desc_start.  returns: the first candidate of the second group.
+static int balanced_split(const LayoutPlan& pl, int K) {
+    double tot = 0, run = 0;
+    for (const SegDesc& d : pl.descs) tot += (double)d.cc * d.rows_p;
+    int split = 1;
+    for (int k = 0; k < K - 1; ++k) {
+        for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) run += (double)pl.descs[j].cc * pl.descs[j].rows_p;
+        split = k + 1;
+        if (run >= tot / 2) break;
+    }
+    return split;
+}
+
+// Row blocks r0 .. r0 + nrows - 1 of a descriptor as a unit of their own (SegDesc::rb0 / seg_nrb; w_off points at row block r0 of the chunk)
+static SegDesc row_block_unit(const SegDesc& d, int r0, int nrows) {
+    SegDesc u = d;
+    u.rb0 = r0; u.rows_p = 16 * nrows; u.seg_nrb = d.rows_p / 16;
+    u.w_off = d.w_off + (int64_t)r0 * (d.cc / 16) * 256;
+    return u;
+}
+
+// Small R (1, 2 or 4 row blocks): the feature segments of `all` regrouped tap-major (sweep_tap_body), up to STEP_NW / nrb segments of one
+// tap chunk per workgroup, largest first; the other segments go to `rest`.
+static std::vector<TapDesc> tap_major_units(const std::vector<SegDesc>& all, int per_wg, std::vector<SegDesc>& rest) {
+    std::vector<TapDesc> taps;
+    std::vector<const SegDesc*> feat;
+    for (const SegDesc& d : all) { if (d.kind <= KIND_V) feat.push_back(&d); else rest.push_back(d); }
+    std::stable_sort(feat.begin(), feat.end(), [](const SegDesc* x, const SegDesc* y) {
+        if (x->kind != y->kind) return x->kind < y->kind;
+        if (x->tap != y->tap) return x->tap < y->tap;
+        if (x->cc != y->cc) return x->cc < y->cc;
+        return x->k0 < y->k0;
+    });
+    for (size_t i0 = 0; i0 < feat.size();) {
+        TapDesc t;
+        memset(&t, 0, sizeof(t));
+        const SegDesc* f0 = feat[i0];
+        t.kind = f0->kind; t.tap = f0->tap; t.k0 = f0->k0; t.cc = f0->cc; t.rows_p = f0->rows_p; t.width = f0->width;
+        while (i0 < feat.size() && t.nitems < per_wg && feat[i0]->kind == t.kind && feat[i0]->tap == t.tap &&
+               feat[i0]->k0 == t.k0 && feat[i0]->cc == t.cc) {
+            t.cand[t.nitems] = feat[i0]->cand; t.cell[t.nitems] = feat[i0]->cell;
+            t.part_idx[t.nitems] = feat[i0]->part_idx; t.w_off[t.nitems] = feat[i0]->w_off;
+            ++t.nitems; ++i0;
         }
-        if (pl.same_group) ngroups = 1;
-        // the chain of one candidate over 4 CUs (chain.hip.h, chain_split): eight row blocks, one batch tile, <= 4 class blocks, no alphas
-        // — in the same-group launch, and in the two-group launches while the chain bounds them (< 28 candidates: sweep(8 candidates) = 36 us
-        // against a 47 us chain; beyond, the chain hides under the other group's sweep and 4 x 64 chain workgroups would only take CUs from it)
-        pl.chain_split = ((pl.same_group || (ngroups == 2 && K < 28)) && !pl.lean_chain && !pl.persist && g.MB == 1 && g.nrb == 8 && g.ncb <= 4 && !g.alphas &&
-                          tu.chain_split != 0 && tu.chain_split != 1) ? 4 : 0;
-        int split = K;
-        if (ngroups == 2) {
-            double tot = 0, run = 0;
-            for (const SegDesc& d : pl.descs) tot += (double)d.cc * d.rows_p;
-            split = 1;
-            for (int k = 0; k < K - 1; ++k) {
-                for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) run += (double)pl.descs[j].cc * pl.descs[j].rows_p;
-                split = k + 1;
-                if (run >= tot / 2) break;
-            }
-        }
-        for (int gi = 0; gi < ngroups; ++gi) {
-            pl.groups.emplace_back();
-            GroupPlan& gr = pl.groups.back();
-            gr.c0 = gi == 0 ? 0 : split;
-            gr.nc = gi == 0 ? split : K - split;
-            std::vector<SegDesc> all(pl.descs.begin() + pl.desc_start[gr.c0], pl.descs.begin() + pl.desc_start[gr.c0 + gr.nc]);
-            for (const SegDesc& d : all) {
-                gr.alg_state += 24.0 * d.rows * std::max(0, std::min(d.cc, d.cols - d.k0));
-                if (d.kind <= KIND_V) gr.alg_feat += (double)hp->B * d.cc;
-            }
-            // small R (1, 2 or 4 row blocks): feature segments are regrouped tap-major (sweep_tap_body)
-            std::vector<SegDesc>& sorted = gr.descs;
-            std::vector<TapDesc>& taps = gr.taps;
-            // (tap-major workgroups stage a batch's rows ONCE for several candidates: not with per-candidate sample orders)
-            const bool tap_major = !wide && (g.nrb == 1 || g.nrb == 2 || g.nrb == 4) && !tu.no_tap_major && !pl.persist && !pl.same_group &&
-                                   !hp->order_per_candidate;
-            if (tap_major) {
-                const int per_wg = STEP_NW / g.nrb;
-                std::vector<const SegDesc*> feat;
-                for (const SegDesc& d : all) { if (d.kind <= KIND_V) feat.push_back(&d); else sorted.push_back(d); }
-                std::stable_sort(feat.begin(), feat.end(), [](const SegDesc* x, const SegDesc* y) {
-                    if (x->kind != y->kind) return x->kind < y->kind;
-                    if (x->tap != y->tap) return x->tap < y->tap;
-                    if (x->cc != y->cc) return x->cc < y->cc;
-                    return x->k0 < y->k0;
-                });
-                for (size_t i0 = 0; i0 < feat.size();) {
-                    TapDesc t;
-                    memset(&t, 0, sizeof(t));
-                    const SegDesc* f0 = feat[i0];
-                    t.kind = f0->kind; t.tap = f0->tap; t.k0 = f0->k0; t.cc = f0->cc; t.rows_p = f0->rows_p; t.width = f0->width;
-                    while (i0 < feat.size() && t.nitems < per_wg && feat[i0]->kind == t.kind && feat[i0]->tap == t.tap &&
-                           feat[i0]->k0 == t.k0 && feat[i0]->cc == t.cc) {
-                        t.cand[t.nitems] = feat[i0]->cand; t.cell[t.nitems] = feat[i0]->cell;
-                        t.part_idx[t.nitems] = feat[i0]->part_idx; t.w_off[t.nitems] = feat[i0]->w_off;
-                        ++t.nitems; ++i0;
-                    }
-                    taps.push_back(t);
+        taps.push_back(t);
+    }
+    std::stable_sort(taps.begin(), taps.end(), [](const TapDesc& x, const TapDesc& y) { return x.nitems * x.cc > y.nitems * y.cc; });
+    return taps;
+}
+
+// wide units: <= 8 row blocks (one per wave) x <= 8 k-blocks of a layout chunk, candidate-major (train-mode single batches
+// launch one candidate's range).  The plane layout is the batch-resident one — OUT / HEAD stay ONE chunk of Rp columns, which the
+// chain, the dev pass and the packers index — so their units name a k-block range inside it (SegDesc::sub_kb0 / sub_nkb).
+// writes: pl.wide_start.
+static std::vector<SegDesc> wide_units(int K, LayoutPlan& pl) {
+    std::vector<SegDesc> fine;
+    pl.wide_start.assign(K + 1, 0);
+    for (int k = 0; k < K; ++k) {
+        pl.wide_start[k] = (int)fine.size();
+        for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) {
+            const SegDesc& d = pl.descs[j];
+            const int nrb_d = d.rows_p / 16, nkb_d = d.cc / 16;
+            for (int r0 = 0; r0 < nrb_d; r0 += WIDE_RBG)
+                for (int q0 = 0; q0 < nkb_d; q0 += WIDE_KB) {
+                    SegDesc u = row_block_unit(d, r0, std::min(WIDE_RBG, nrb_d - r0));
+                    u.sub_kb0 = q0; u.sub_nkb = std::min(WIDE_KB, nkb_d - q0);
+                    fine.push_back(u);
                 }
-                std::stable_sort(taps.begin(), taps.end(), [](const TapDesc& x, const TapDesc& y) { return x.nitems * x.cc > y.nitems * y.cc; });
-                if (taps.size() < 192 && !tu.force_tap_major) {   // too few workgroups to fill 256 CUs: per-segment path
-                    taps.clear();
-                    sorted = all;
-                }
-            } else {
-                sorted = all;
-            }
-            if (wide) {
-                // wide units: <= 8 row blocks (one per wave) x <= 8 k-blocks of a layout chunk, candidate-major (train-mode single batches
-                // launch one candidate's range).  The plane layout is the batch-resident one — OUT / HEAD stay ONE chunk of Rp columns, which the
-                // chain, the dev pass and the packers index — so their units name a k-block range inside it (SegDesc::sub_kb0 / sub_nkb).
-                std::vector<SegDesc> fine;
-                pl.wide_start.assign(K + 1, 0);
-                for (int k = gr.c0; k < gr.c0 + gr.nc; ++k) {
-                    pl.wide_start[k] = (int)fine.size();
-                    for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) {
-                        const SegDesc& d = pl.descs[j];
-                        const int nrb_d = d.rows_p / 16, nkb_d = d.cc / 16;
-                        for (int r0 = 0; r0 < nrb_d; r0 += WIDE_RBG)
-                            for (int q0 = 0; q0 < nkb_d; q0 += WIDE_KB) {
-                                SegDesc u = d;
-                                u.rb0 = r0; u.rows_p = 16 * std::min(WIDE_RBG, nrb_d - r0); u.seg_nrb = nrb_d;
-                                u.w_off = d.w_off + (int64_t)r0 * nkb_d * 256;
-                                u.sub_kb0 = q0; u.sub_nkb = std::min(WIDE_KB, nkb_d - q0);
-                                fine.push_back(u);
-                            }
-                    }
-                }
-                pl.wide_start[K] = (int)fine.size();
-                sorted.swap(fine);
-            } else
-            std::stable_sort(sorted.begin(), sorted.end(), [](const SegDesc& x, const SegDesc& y) {
-                return (int64_t)x.cc * x.rows_p > (int64_t)y.cc * y.rows_p; });
-            if (pl.same_group) {
-                // OUT / HEAD units one ROW BLOCK each (round 6): as ONE workgroup per 128 x 128 segment every wave walked its row block's eight
-                // tiles in four dependent load -> Adam -> store rounds of ~2.5 us behind the dy it waits for — OUT_1, released by the LAST dy of
-                // the step, ended 12.7 us after the chain where the cell-0 feature units end after 6.2 (profiles/r06_chain_split_r128.log).
-                // Row-split units (SegDesc::rb0 / seg_nrb, one tile per wave: the k-split walk) update the same tiles with the same arithmetic.
-                std::vector<SegDesc> fine;
-                for (const SegDesc& d : sorted) {
-                    const int nrb_d = d.rows_p / 16;
-                    if (d.kind <= KIND_V || nrb_d <= 1) { fine.push_back(d); continue; }
-                    for (int r0 = 0; r0 < nrb_d; ++r0) {
-                        SegDesc u = d;
-                        u.rb0 = r0; u.rows_p = 16; u.seg_nrb = nrb_d;
-                        u.w_off = d.w_off + (int64_t)r0 * (d.cc / 16) * 256;
-                        fine.push_back(u);
-                    }
-                }
-                sorted.swap(fine);
-            }
-            if (pl.same_group)   // the order the chain releases the units in
-                std::stable_sort(sorted.begin(), sorted.end(), [](const SegDesc& x, const SegDesc& y) {
-                    // (the slot each unit waits for: feature units of cell i -> i, OUT_i -> i - 1, HEAD -> the last cell; highest slot first)
-                    auto slot = [](const SegDesc& d) { return d.kind == KIND_HEAD ? MFAS_MAX_CELLS : (d.kind == KIND_OUT ? d.cell - 1 : d.cell); };
-                    return slot(x) > slot(y);
-                });
         }
     }
-    // reduce-in-sweep: one group (the chain is on the critical path), general chain, per-segment units only
+    pl.wide_start[K] = (int)fine.size();
+    return fine;
+}
+
+// The same-group launch's units.  OUT / HEAD units one ROW BLOCK each (round 6): as ONE workgroup per 128 x 128 segment every wave walked
+// its row block's eight tiles in four dependent load -> Adam -> store rounds of ~2.5 us behind the dy it waits for — OUT_1, released by the
+// LAST dy of the step, ended 12.7 us after the chain where the cell-0 feature units end after 6.2 (profiles/r06_chain_split_r128.log).
+// Row-split units (one tile per wave: the k-split walk) update the same tiles with the same arithmetic.  Then the order the chain releases
+// the units in.
+static std::vector<SegDesc> same_group_units(const std::vector<SegDesc>& sorted) {
+    std::vector<SegDesc> fine;
+    for (const SegDesc& d : sorted) {
+        const int nrb_d = d.rows_p / 16;
+        if (d.kind <= KIND_V || nrb_d <= 1) { fine.push_back(d); continue; }
+        for (int r0 = 0; r0 < nrb_d; ++r0) fine.push_back(row_block_unit(d, r0, 1));
+    }
+    std::stable_sort(fine.begin(), fine.end(), [](const SegDesc& x, const SegDesc& y) {
+        // (the slot each unit waits for: feature units of cell i -> i, OUT_i -> i - 1, HEAD -> the last cell; highest slot first)
+        auto slot = [](const SegDesc& d) { return d.kind == KIND_HEAD ? MFAS_MAX_CELLS : (d.kind == KIND_OUT ? d.cell - 1 : d.cell); };
+        return slot(x) > slot(y);
+    });
+    return fine;
+}
+
+// Stage 7, one group's work list: candidates c0 .. c0 + nc - 1.  reads: the inputs, the schedule, Geo, descs, desc_start.
+// returns: the group with its per-segment units (largest first; wide: candidate-major; same-group: release order) and tap-major units.
+static GroupPlan group_work_list(const PlanIn& in, Sched s, int c0, int nc, LayoutPlan& pl) {
+    const Geo& g = pl.g;
+    GroupPlan gr;
+    gr.c0 = c0; gr.nc = nc;
+    std::vector<SegDesc> all(pl.descs.begin() + pl.desc_start[c0], pl.descs.begin() + pl.desc_start[c0 + nc]);
+    for (const SegDesc& d : all) {
+        gr.alg_state += 24.0 * d.rows * std::max(0, std::min(d.cc, d.cols - d.k0));
+        if (d.kind <= KIND_V) gr.alg_feat += (double)in.hp->B * d.cc;
+    }
+    if (s == Sched::Wide) { gr.descs = wide_units(in.K, pl); return gr; }
+    // (tap-major workgroups stage a batch's rows ONCE for several candidates: not with per-candidate sample orders)
+    if (launch_per_phase(s) && (g.nrb == 1 || g.nrb == 2 || g.nrb == 4) && !in.tu.no_tap_major && !in.hp->order_per_candidate) {
+        gr.taps = tap_major_units(all, STEP_NW / g.nrb, gr.descs);
+        if (gr.taps.size() < 192 && !in.tu.force_tap_major) gr.taps.clear();      // too few workgroups to fill 256 CUs: per-segment path
+    }
+    if (gr.taps.empty()) gr.descs = std::move(all);
+    std::stable_sort(gr.descs.begin(), gr.descs.end(), [](const SegDesc& x, const SegDesc& y) {
+        return (int64_t)x.cc * x.rows_p > (int64_t)y.cc * y.rows_p; });
+    if (s == Sched::SameGroup) gr.descs = same_group_units(gr.descs);
+    return gr;
+}
+
+// What follows from the schedule once the units are known.  reads: the schedule, groups, lds_step.  writes: red_in_sweep, defer.
+static void unit_dependent_flags(const PlanIn& in, Sched s, LayoutPlan& pl) {
+    bool tap_units = false, double_pass_fits = true;
+    for (const GroupPlan& gr : pl.groups) {
+        tap_units = tap_units || !gr.taps.empty();
+        for (const SegDesc& d : gr.descs)
+            if (d.kind <= KIND_V && sweep_unit_lds_double(pl.g, d) > pl.lds_step) double_pass_fits = false;
+    }
+    // reduce-in-sweep: the chain is on the critical path, general chain, per-segment units only (tap-major workgroups serve several candidates)
     // (beyond ~28 candidates the co-scheduled chain is hidden anyway and the extra write-through traffic costs: 29.0 vs 26.7 cand/s at 32)
     // (not with chain_split: the reducing unit's drain + arrival + summing pass behind the LAST dy of the step ends the launch 3.5 us later,
     //  while the chain's four parts sum their own row blocks of the slabs at entry, every load in flight at once; measured, K = 1: 41.3 with
     //  the reduction in the sweep, 38.4 without, 43.0 with a hybrid — cells >= 1 in the sweep, cell 0 in the chain — profiles/r06_chain_split_r128.log)
-    pl.red_in_sweep = !wide && K < 28 && !pl.lean_chain && !pl.persist && !tu.no_red_in_sweep && !(pl.chain_split && pl.same_group);
-    for (const auto& gr : pl.groups) if (!gr.taps.empty()) pl.red_in_sweep = false;     // (tap-major workgroups serve several candidates)
-    if (pl.chain_split) {
-        pl.lds_split = std::max(pl.lds_step, chain_split_lds_floats<4>(g.Rp, g.Cp) * 4);
-        if ((size_t)K * XCH_CAND_FLOATS >= (1ull << 30)) return fail(MFAS_EINVAL, "internal: exchange area beyond the 32-bit buffer offsets");
-    }
-    // measured crossover (MI355X, B=20): R=16 between 165 and 330 MB of group state per launch, R=128 between 300 and 600 MB
-    // (the spilling chain of the occupancy build takes ~40 / ~125 us there)
-    pl.occ_bytes = g.nrb >= 8 ? 450e6 : 250e6;
-    if (tu.occ_bytes >= 0) pl.occ_bytes = tu.occ_bytes;
-    if (pl.persist) {
-        std::vector<int> res_cand;      // candidate of every resident unit, in unit order
-        // unit list of the resident schedule: the feature units (the resident lean chain updates OUT / HEAD itself)
-        pl.need.assign(K, 0);
-        for (const SegDesc& d : pl.descs)
-            if (d.kind <= KIND_V) { pl.pdescs.push_back(d); res_cand.push_back(d.cand); pl.need[d.cand]++; }
-        if (!tu.no_xcd_placement) {
-            // XCD-aware placement (round 5): consecutive workgroups of a launch are dealt round-robin to the 8 XCDs (block b -> XCD b % 8,
-            // MI355X_MICROARCH.md), each with its own L2.  A candidate's chain and the workgroups that hold its units exchange 60 KB of
-            // slabs and 8 KB of dy per step: deal the roles so that they share an XCD wherever its 32 slots allow (greedy, candidate by
-            // candidate; two-unit workgroups are grouped by their FIRST unit's candidate, and the chain of a candidate that only ever
-            // comes second goes where most of its units are).  Placement only: the exchanges do not depend on it.
-            // (NX: 8 XCDs on MI355X in SPX mode, block b -> XCD b % 8; MFAS_XCDS=n for another partition mode.  A wrong NX costs
-            //  only the co-location.  prim / sec below mirror sweep_resident's unit mapping — unit u of workgroup w is unit w + u * nwg,
-            //  persist.hip.h `const int ui = wg + u * nwg` — and must change with it.)
-            const int nwg = pl.nres_wg, G = K + nwg, NX = tu.n_xcd > 0 ? std::min(tu.n_xcd, 64) : 8;
-            std::vector<std::vector<int>> slots(NX);
-            for (int b = G - 1; b >= 0; --b) slots[b % NX].push_back(b);       // (pop_back hands out the lowest block of an XCD first)
-            std::vector<int32_t> role(G, -1);
-            std::vector<int> chain_xcd(K, -1);
-            std::vector<char> wg_done(nwg, 0);
-            auto take = [&](int x, int item) { role[slots[x].back()] = item; slots[x].pop_back(); };
-            auto roomiest = [&]() { int bx = 0; for (int x = 1; x < NX; ++x) if (slots[x].size() > slots[bx].size()) bx = x; return bx; };
-            std::vector<int> prim(nwg), sec(nwg, -1);
-            for (int w = 0; w < nwg; ++w) {
-                prim[w] = res_cand[w];
-                if (pl.res_nu == 2 && w + nwg < (int)res_cand.size()) sec[w] = res_cand[w + nwg];
-            }
-            for (int c = 0; c < K; ++c) {                   // candidates that come first in some workgroup: chain + those workgroups
-                bool any = false;
-                for (int w = 0; w < nwg; ++w) any = any || prim[w] == c;
-                if (!any) continue;
-                const int x = roomiest();
-                if (!slots[x].empty()) { take(x, c); chain_xcd[c] = x; }
-                for (int w = 0; w < nwg; ++w)
-                    if (prim[w] == c && !wg_done[w] && !slots[x].empty()) { take(x, K + w); wg_done[w] = 1; }
-            }
-            std::vector<int> wg_xcd(nwg, -1);
-            for (int b = 0; b < G; ++b) if (role[b] >= K) wg_xcd[role[b] - K] = b % NX;
-            for (int c = 0; c < K; ++c) {                   // chains not placed yet: where most of the candidate's units are
-                if (chain_xcd[c] >= 0) continue;
-                std::vector<int> votes(NX, 0);
-                for (int w = 0; w < nwg; ++w) if ((prim[w] == c || sec[w] == c) && wg_xcd[w] >= 0) votes[wg_xcd[w]]++;
-                int bx = -1;
-                for (int x = 0; x < NX; ++x) if (!slots[x].empty() && (bx < 0 || votes[x] > votes[bx])) bx = x;
-                if (bx >= 0) { take(bx, c); chain_xcd[c] = bx; }
-            }
-            for (int w = 0; w < nwg; ++w)                   // whatever did not fit its XCD
-                if (!wg_done[w]) { const int x = roomiest(); take(x, K + w); wg_done[w] = 1; }
-            bool ok = true;
-            for (int b = 0; b < G; ++b) ok = ok && role[b] >= 0;
-            if (ok) pl.role = role;
-        }
-    }
-    // W/m/v beyond what the 256 MiB Infinity Cache can keep between steps are streamed nontemporally
-    pl.nontemporal = (double)pl.plane_stride * 12.0 > 200.0 * 1024 * 1024;
-    if (tu.nt >= 0) pl.nontemporal = tu.nt != 0;
+    pl.red_in_sweep = (launch_per_phase(s) || s == Sched::SameGroup) && in.K < 28 && !pl.lean_chain && !in.tu.no_red_in_sweep &&
+                      !(pl.chain_split && s == Sched::SameGroup) && !tap_units;
     // deferred stores (launches.hip.h, mark_deferred): the two-group launch-per-phase schedule with the general chain, no alphas (the
     // replayed step would need its gradient scale too) and per-segment feature units only, where every feature unit's double pass — a plain
     // unit's three staged tiles + the replayed step's rows and dy — fits the LDS the plan already asks for (lds_step is NOT raised for it)
-    pl.defer = pl.groups.size() == 2 && !wide && !pl.persist && !pl.same_group && !pl.lean_chain && !g.alphas;
-    for (const GroupPlan& gr : pl.groups) {
-        if (!gr.taps.empty()) pl.defer = false;
-        for (const SegDesc& d : gr.descs)
-            if (d.kind <= KIND_V && sweep_unit_lds_double(g, d) > pl.lds_step) pl.defer = false;
+    pl.defer = s == Sched::TwoGroups && !pl.lean_chain && !pl.g.alphas && !tap_units && double_pass_fits;
+}
+
+// Stage 8, the resident schedule's unit list and XCD role table.  reads: descs, nres_wg, res_nu.  writes: pdescs, need, role.
+static void resident_units_and_roles(const PlanIn& in, LayoutPlan& pl) {
+    const int K = in.K;
+    std::vector<int> res_cand;      // candidate of every resident unit, in unit order
+    // unit list of the resident schedule: the feature units (the resident lean chain updates OUT / HEAD itself)
+    pl.need.assign(K, 0);
+    for (const SegDesc& d : pl.descs)
+        if (d.kind <= KIND_V) { pl.pdescs.push_back(d); res_cand.push_back(d.cand); pl.need[d.cand]++; }
+    if (in.tu.no_xcd_placement) return;
+    // XCD-aware placement (round 5): consecutive workgroups of a launch are dealt round-robin to the 8 XCDs (block b -> XCD b % 8,
+    // MI355X_MICROARCH.md), each with its own L2.  A candidate's chain and the workgroups that hold its units exchange 60 KB of
+    // slabs and 8 KB of dy per step: deal the roles so that they share an XCD wherever its 32 slots allow (greedy, candidate by
+    // candidate; two-unit workgroups are grouped by their FIRST unit's candidate, and the chain of a candidate that only ever
+    // comes second goes where most of its units are).  Placement only: the exchanges do not depend on it.
+    // (NX: 8 XCDs on MI355X in SPX mode, block b -> XCD b % 8; MFAS_XCDS=n for another partition mode.  A wrong NX costs
+    //  only the co-location.  prim / sec below mirror sweep_resident's unit mapping — unit u of workgroup w is unit w + u * nwg,
+    //  persist.hip.h `const int ui = wg + u * nwg` — and must change with it.)
+    const int nwg = pl.nres_wg, G = K + nwg, NX = in.tu.n_xcd > 0 ? std::min(in.tu.n_xcd, 64) : 8;
+    std::vector<std::vector<int>> slots(NX);
+    for (int b = G - 1; b >= 0; --b) slots[b % NX].push_back(b);       // (pop_back hands out the lowest block of an XCD first)
+    std::vector<int32_t> role(G, -1);
+    std::vector<int> chain_xcd(K, -1);
+    std::vector<char> wg_done(nwg, 0);
+    auto take = [&](int x, int item) { role[slots[x].back()] = item; slots[x].pop_back(); };
+    auto roomiest = [&]() { int bx = 0; for (int x = 1; x < NX; ++x) if (slots[x].size() > slots[bx].size()) bx = x; return bx; };
+    std::vector<int> prim(nwg), sec(nwg, -1);
+    for (int w = 0; w < nwg; ++w) {
+        prim[w] = res_cand[w];
+        if (pl.res_nu == 2 && w + nwg < (int)res_cand.size()) sec[w] = res_cand[w + nwg];
     }
-    if (pl.defer) {
-        // the replayed step's dy must outlive the group's next chain: a second dy area at the END of every candidate's step-buffer block
-        // (no existing sub-offset moves); the host alternates Geo::sb_dy between the two in the per-launch arguments (train.hip.h)
-        pl.sb_dy_alt = g.sb_size;
-        g.sb_size = (g.sb_size + (int64_t)MFAS_MAX_CELLS * g.Bp * g.Rp + 63) & ~63LL;
-        for (int k = 0; k < K; ++k) pl.cands[k].step_off = (int64_t)k * g.sb_size;
-        pl.step_total = (int64_t)K * g.sb_size;
+    for (int c = 0; c < K; ++c) {                   // candidates that come first in some workgroup: chain + those workgroups
+        bool any = false;
+        for (int w = 0; w < nwg; ++w) any = any || prim[w] == c;
+        if (!any) continue;
+        const int x = roomiest();
+        if (!slots[x].empty()) { take(x, c); chain_xcd[c] = x; }
+        for (int w = 0; w < nwg; ++w)
+            if (prim[w] == c && !wg_done[w] && !slots[x].empty()) { take(x, K + w); wg_done[w] = 1; }
     }
+    std::vector<int> wg_xcd(nwg, -1);
+    for (int b = 0; b < G; ++b) if (role[b] >= K) wg_xcd[role[b] - K] = b % NX;
+    for (int c = 0; c < K; ++c) {                   // chains not placed yet: where most of the candidate's units are
+        if (chain_xcd[c] >= 0) continue;
+        std::vector<int> votes(NX, 0);
+        for (int w = 0; w < nwg; ++w) if ((prim[w] == c || sec[w] == c) && wg_xcd[w] >= 0) votes[wg_xcd[w]]++;
+        int bx = -1;
+        for (int x = 0; x < NX; ++x) if (!slots[x].empty() && (bx < 0 || votes[x] > votes[bx])) bx = x;
+        if (bx >= 0) { take(bx, c); chain_xcd[c] = bx; }
+    }
+    for (int w = 0; w < nwg; ++w)                   // whatever did not fit its XCD
+        if (!wg_done[w]) { const int x = roomiest(); take(x, K + w); wg_done[w] = 1; }
+    bool ok = true;
+    for (int b = 0; b < G; ++b) ok = ok && role[b] >= 0;
+    if (ok) pl.role = role;
+}
+
+// Stage 9, the step buffers (same geometry for every candidate: sized for the largest).  A deferring plan's replayed step needs its dy to
+// outlive the group's next chain: a second dy area at the END of every candidate's block (no other sub-offset depends on it); the host
+// alternates Geo::sb_dy between the two in the per-launch arguments (train.hip.h).
+// reads: Geo, defer.  writes: Geo::sb_*, sb_dy_alt, cands[k].step_off, step_total.
+static void layout_step_buffers(int K, int max_slots, LayoutPlan& pl) {
+    Geo& g = pl.g;
+    const int64_t br = (int64_t)g.Bp * g.Rp;
+    int64_t o = 0;
+    g.sb_part = o; o += (int64_t)max_slots * br;
+    g.sb_dy = o; o += MFAS_MAX_CELLS * br;
+    g.sb_xo = o; o += MFAS_MAX_CELLS * br;
+    g.sb_dlog = o; o += (int64_t)g.Bp * g.Cp;
+    g.sb_sav = o; o += 3 * MFAS_MAX_CELLS * br;
+    g.sb_yf = o; o += 2 * MFAS_MAX_CELLS * br;
+    g.sb_gsc = o; o += 16;
+    o = (o + 63) & ~63LL;
+    if (pl.defer) { pl.sb_dy_alt = o; o = (o + MFAS_MAX_CELLS * br + 63) & ~63LL; }
+    g.sb_size = o;
+    for (int k = 0; k < K; ++k) pl.cands[k].step_off = (int64_t)k * g.sb_size;
+    pl.step_total = (int64_t)K * g.sb_size;
+}
+
+// One plan for one kernel family (wide or batch-resident): the stages in order.
+static int plan_layout_as(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int K, int chunk_cols,
+                          int n_cus, bool allow_persist, const Tuning& tu, const bool wide, LayoutPlan& pl) {
+    const PlanIn in{hp, confs, n_cells, drop_seeds, K, chunk_cols, n_cus, allow_persist, tu, wide};
+    pl = LayoutPlan();
+    pl.wide = wide;
+    pl.g = make_geo(hp);
+    const ChunkPlan lp = choose_chunk(in, pl.g);
+    pl.chunk = lp.target;
+    const int max_slots = layout_candidates(in, pl);
+    lds_budgets(in, lp, pl);
+    dev_pass_and_streaming(in, pl);
+    const Sched s = choose_schedule(in, pl);
+    if (int rc = schedule_flags(in, s, pl)) return rc;
+    const int split = s == Sched::TwoGroups ? balanced_split(pl, K) : K;
+    pl.groups.push_back(group_work_list(in, s, 0, split, pl));
+    if (split < K) pl.groups.push_back(group_work_list(in, s, split, K - split, pl));
+    unit_dependent_flags(in, s, pl);
+    if (s == Sched::Resident) resident_units_and_roles(in, pl);
+    layout_step_buffers(K, max_slots, pl);
     return MFAS_OK;
 }
 
