@@ -192,6 +192,37 @@ int mfas_population_move(mfas_population* dst, int32_t kd, mfas_population* src,
 int mfas_population_forward(mfas_population* pop, int32_t k, const mfas_table* tab, int64_t row0,
                             int64_t nrows, float* logits, int64_t* corrects);
 
+/* Scores M candidates of the population on every row of a table, one by one AND together, in one call: the population form of
+ * test_ntu_track_acc (train_searchable/ntu.py:92-125; main_found_ntu.py lists five found configurations).  No reference counterpart
+ * for the ensemble.  Every member runs in eval mode exactly as the dev pass of mfas_population_train does (the same kernel, the same
+ * statistics path: member_stats ARE the dev pass's dev_loss_sum / dev_corrects for that table).
+ *   plane:    0 = the live parameters, 3 = the kept best-epoch parameters of an unfinished snapshot_best schedule (MFAS_EINVAL when
+ *             a member keeps none, as mfas_population_get_params).
+ *   members:  HOST [M] candidate indices, repeats allowed; NULL = 0..K-1 (M must then be K).
+ *   weights:  HOST [M], each finite and >= 0, sum > 0; NULL = uniform.  Normalised on the host in double, then rounded to float.
+ *   combine:  a member's SCORE row z is its logits (multitask: (logits + vlogit) + slogit in float32, what the dev pass compares);
+ *             its PROBABILITY row is softmax(z - max z) (loss_mode 1: sigmoid(z)).
+ *             0: the ensemble's probabilities are sum_m w_m * p_m, summed in list order; 1: they are the probability row of
+ *             sum_m w_m * z_m.
+ *   decision: loss_mode 0: the FIRST maximum of the ensemble's probabilities (ties to the lower class, like the dev pass);
+ *             loss_mode 1: probability > f1_threshold, F1 'samples' in 32.32 fixed point like the dev pass.
+ *   loss:     loss_mode 0: -log max(p[label], 2^-126) per row; loss_mode 1 with combine 1: the weighted BCE of the mean score;
+ *             loss_mode 1 with combine 0: REPORTED AS 0 (a mean of probabilities has no score to take the BCE of).
+ *   scratch_bytes: device scratch for the members' logits of one block of rows (0 = 64 MiB; at least one row of M * C floats): the
+ *             table is walked in row blocks of that size.  The ensemble's outputs are bit-identical for every value.
+ *   member_stats: HOST [M] or NULL (train_* = 0).  member_preds: DEVICE int32 [M][N] or NULL, every member's own decision
+ *             (loss_mode 0 only).  scores: DEVICE float (N, C) or NULL, the ensemble's probabilities.  ensemble_stats: HOST [1] or
+ *             NULL: dev_loss_sum / dev_corrects of the ensemble (train_* = 0).
+ * Nothing a later train call reads is touched (parameters, moments, kept best, progress, status, statistics, the launch record):
+ * the call works in an arena of its own on the population's stream and synchronises once, for the final copy of the statistics.
+ * MFAS_EINVAL, with a message naming the value, and nothing changed: a member index outside [0, K); M <= 0; members == NULL with
+ * M != K; a negative or non-finite weight or a zero weight sum; plane not 0 / 3; combine not 0 / 1; member_preds with loss_mode 1;
+ * scratch_bytes below one row; a table mfas_population_forward refuses. */
+int mfas_population_evaluate(mfas_population* pop, const mfas_table* tab, int32_t plane, const int32_t* members,
+                             const float* weights, int32_t M, int32_t combine, int64_t scratch_bytes,
+                             mfas_epoch_stats* member_stats, int32_t* member_preds, float* scores,
+                             mfas_epoch_stats* ensemble_stats);
+
 /* Replaces Searchable_Skeleton_Image_Net.forward in TRAIN mode (ntu_searchable.py:206-247 with model.train(True)) for
  * candidate k on ONE batch = rows [row0, row0+nrows) of a table, nrows <= hyper.B: batch-statistics BatchNorm (the running
  * statistics are updated, as any train-mode forward does), dropout from the candidate's stream at `step_index`; writes

@@ -2,7 +2,9 @@
 """Train / test one found fusion architecture — counterpart of /root/reference/main_found_ntu.py (flags :24-68,
 confs :173-182) on the MI355X engine with precomputed taps.  Phase 1 = 1 epoch on central_params (:108-123);
 phase 2 = `--epochs` epochs with a fresh Adam + scheduler (:128-137) — restricted to the central parameters because
-the backbones are feature tables here (fine-tuning them needs raw video: out of scope); then the test pass (:152)."""
+the backbones are feature tables here (fine-tuning them needs raw video: out of scope); then the test pass (:152).
+`--ensemble CONF [CONF ...]` (no reference counterpart; off by default) trains several entries of CONFS as one population on the
+search schedule and prints each one's test accuracy and their ensemble's (Population.evaluate)."""
 import argparse
 import time
 
@@ -44,7 +46,36 @@ def parse_args(argv=None):
     p.add_argument("--synthetic", type=int, nargs=3, metavar=("N_TRAIN", "N_DEV", "N_TEST"), default=None)
     p.add_argument("--feature_dtype", default="bf16", choices=["bf16", "f16", "f32"])
     p.add_argument("--seed", type=int, default=0)
-    return p.parse_args(argv)
+    p.add_argument("--ensemble", type=int, nargs="+", metavar="CONF", default=None, choices=sorted(CONFS),
+                   help="train these entries of CONFS as ONE population and print each one's test accuracy and their ensemble's "
+                        "(mean of the members' probabilities).  The members are trained on the single-phase SEARCH schedule "
+                        "(train_sampled_models: --epochs epochs, one Adam, no phase-1 pretraining), not the two-phase schedule of "
+                        "--conf.  Needs --no-multitask (the search-mode train loop refuses multitask); single process only.")
+    args = p.parse_args(argv)
+    if args.ensemble is not None and args.multitask:
+        p.error("--ensemble needs --no-multitask: the search-mode train loop refuses multitask")
+    return args
+
+
+def train_ensemble(args, loaders, device):
+    """--ensemble: the listed configurations through train_sampled_models(..., return_model=all), their parameters into ONE
+    population, one evaluate call over the test split.  Returns (per-configuration test accuracies, the ensemble's)."""
+    import mfas_amd as M
+    confs = [np.array(CONFS[c]) for c in args.ensemble]
+    _, models = M.train_sampled_models(confs, M.Searchable_Skeleton_Image_Net, loaders, args, device,
+                                       return_model=list(range(len(confs))))
+    pop = M.Population(models[0].hyper(False), confs, device)
+    try:
+        for k, m in enumerate(models):
+            pop.set_params(k, m.flat_params())
+        sizes = {x: len(loaders[x].dataset) for x in ("train", "test", "dev")}
+        member, ens = M.test_population_track_acc(pop, loaders, sizes)
+    finally:
+        pop.close()
+    for c, a in zip(args.ensemble, member.tolist()):
+        print("Conf {} test accuracy: {}".format(c, a))
+    print("Ensemble test accuracy: {}".format(float(ens)))
+    return member, ens
 
 
 def train_model(rmode, configuration, dataloaders, args, device):
@@ -92,6 +123,8 @@ def main(argv=None):
     else:
         tabs = {s: M.FeatureTable.load(args.featuredir, s, device) for s in ("train", "dev", "test")}
     loaders = {s: M.FeatureLoader(t, args.batchsize, shuffle=True) for s, t in tabs.items()}
+    if args.ensemble is not None:
+        return train_ensemble(args, loaders, device)
     t0 = time.time()
     acc = train_model(rmode, configuration, loaders, args, device)
     el = time.time() - t0

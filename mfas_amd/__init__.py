@@ -9,6 +9,6 @@ from .ntu_searchable import (Searchable_Skeleton_Image_Net, get_central_states, 
                              get_possible_layer_configurations, set_central_states, train_sampled_models)
 from . import avmnist_searchable, mmimdb_searchable  # noqa: F401
 from .scheduler import FixedScheduler, LRCosineAnnealingScheduler  # noqa: F401
-from .train_ntu import test_ntu_track_acc, train_ntu_track_acc  # noqa: F401
+from .train_ntu import test_ntu_track_acc, test_population_track_acc, train_ntu_track_acc  # noqa: F401
 
 __version__ = "0.1.0"

@@ -20,7 +20,8 @@
 // validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated; plan_dump.hip.h: the
 // plan as text, test-hooks variant only), launches.hip.h (the
 // launches of an epoch as data), builds.hip.h (which build a launch takes, as data: the choice functions, the builds a plan can launch, the
-// tables' row lists), state.hip.h (state in and out, the candidate carry, move, the fallback), train.hip.h (the train call).  Here:
+// tables' row lists), state.hip.h (state in and out, the candidate carry, move, the fallback), train.hip.h (the train call); vote.hip.h (k_vote and the host side of
+// mfas_population_evaluate: members through k_eval, then the vote).  Here:
 // k_step / k_chain, the kernel tables (key -> instantiation: the only place one is named), create / destroy, the C ABI.
 // Dev evaluation is row-parallel (k_eval).  Weights live in a 16x16 tile-major layout that is exactly the
 // MFMA 16x16x4 f32 operand layout, so every W/m/v access is one coalesced 16 B/lane load.
@@ -36,6 +37,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
+#include <cmath>
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -197,6 +199,8 @@ struct mfas_population {
     float* d_scal = nullptr;        // device copy of the step scalars
     size_t scal_cap = 0;
     unsigned long long* d_trace = nullptr;
+    char* d_vote = nullptr;         // mfas_population_evaluate's arena (grow-only; vote.hip.h): nothing a train call reads
+    size_t vote_cap = 0;
 };
 
 // roctx ranges around a train() call and each of its epochs (rocprofv3 --marker-trace shows them next to the kernels).  The
@@ -460,6 +464,7 @@ extern "C" void mfas_population_destroy(mfas_population* p) {
     hipFree(p->d_cellflag);
     hipFree(p->d_xch);
     hipFree(p->d_move);
+    hipFree(p->d_vote);
     hipFree(p->d_sync); hipFree(p->d_need); hipFree(p->d_role); hipFree(p->d_scal); hipFree(p->d_trace); hipFree(p->d_pdescs);
     delete p;
 }
@@ -507,6 +512,7 @@ static hipError_t launch_eval(mfas_population* p, const EvalArgs& a, int ncand, 
 #include "launches.hip.h"
 #include "state.hip.h"
 #include "train.hip.h"
+#include "vote.hip.h"
 
 extern "C" int mfas_population_set_params(mfas_population* p, int32_t k, const float* flat) {
     if (!p || !flat || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad argument");
@@ -616,6 +622,13 @@ extern "C" int mfas_population_forward(mfas_population* p, int32_t k, const mfas
         *corrects = (int64_t)h;
     }
     return MFAS_OK;
+}
+
+extern "C" int mfas_population_evaluate(mfas_population* p, const mfas_table* tab, int32_t plane, const int32_t* members,
+                                        const float* weights, int32_t M, int32_t combine, int64_t scratch_bytes,
+                                        mfas_epoch_stats* member_stats, int32_t* member_preds, float* scores,
+                                        mfas_epoch_stats* ensemble_stats) {
+    return evaluate_impl(p, tab, plane, members, weights, M, combine, scratch_bytes, member_stats, member_preds, scores, ensemble_stats);
 }
 
 extern "C" int mfas_population_forward_train(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0, int32_t nrows,

@@ -478,6 +478,41 @@ class Population:
                                                         C.byref(corr) if count else None))
         return (logits, int(corr.value)) if count else logits
 
+    def evaluate(self, table: FeatureTable, members: Optional[Sequence[int]] = None, weights: Optional[Sequence[float]] = None,
+                 plane: int = 0, combine: str = "prob", scratch_bytes: int = 0, return_scores: bool = False,
+                 return_preds: bool = False):
+        """Score `members` (candidate indices, repeats allowed; None = all K) on every row of `table`, one by one and as a weighted
+        ensemble, in one call (mfas_population_evaluate).  Every member runs the dev pass's eval-mode forward; combine "prob" averages
+        the members' probabilities, "score" their score rows; plane 3 evaluates the kept best-epoch parameters of an unfinished
+        snapshot_best schedule.  Returns {"member_stats": structured array [M] like train()'s, "ensemble": {"loss_sum", "corrects"}
+        (loss_mode 1: corrects is the 32.32 fixed-point F1 sum, and "f1_sum" its float value), "scores": (N, C) device tensor with
+        return_scores, "preds": int32 (M, N) device tensor with return_preds}.  Nothing a later train() reads is changed."""
+        members, weights, combine_i = evaluate_arguments(self.K, members, weights, plane, combine, scratch_bytes,
+                                                         self.hp.loss_mode, return_preds)
+        M = len(members)
+        if self.hp.loss_mode == 0:      # the kernels index by the label
+            table.check_labels(self.hp.C)
+        self._check_table(table)
+        stats = np.zeros(M, dtype=[("train_loss_sum", "f8"), ("dev_loss_sum", "f8"), ("train_corrects", "i8"), ("dev_corrects", "i8")])
+        ens = np.zeros(1, dtype=stats.dtype)
+        N = len(table)
+        scores = torch.empty((N, self.hp.C), dtype=torch.float32, device=self.device) if return_scores else None
+        preds = torch.empty((M, N), dtype=torch.int32, device=self.device) if return_preds else None
+        tc = table.to_c()
+        with torch.cuda.device(self._idx):
+            _lib.check(self.lib.mfas_population_evaluate(
+                self._h, C.byref(tc), int(plane), members.ctypes.data, None if weights is None else weights.ctypes.data, M,
+                combine_i, int(scratch_bytes), stats.ctypes.data, None if preds is None else C.c_void_p(preds.data_ptr()),
+                None if scores is None else C.c_void_p(scores.data_ptr()), ens.ctypes.data))
+        out = {"member_stats": stats, "ensemble": {"loss_sum": float(ens["dev_loss_sum"][0]), "corrects": int(ens["dev_corrects"][0])}}
+        if self.hp.loss_mode == 1:
+            out["ensemble"]["f1_sum"] = float(ens["dev_corrects"][0]) / F1_FIXED_POINT
+        if return_scores:
+            out["scores"] = scores
+        if return_preds:
+            out["preds"] = preds
+        return out
+
     def forward_train(self, k: int, table: FeatureTable, row0: int = 0, nrows: Optional[int] = None, step: int = 0):
         """Train-mode forward of ONE batch (<= hp.B rows): batch-statistics BN (running stats move), dropout stream at `step`."""
         nrows = len(table) - row0 if nrows is None else nrows
@@ -566,6 +601,36 @@ def load_checkpoint(path: str, pop: Population):
 
 
 F1_FIXED_POINT = float(1 << 32)
+
+
+def evaluate_arguments(K: int, members, weights, plane, combine, scratch_bytes, loss_mode: int, return_preds: bool):
+    """Population.evaluate's argument checks, a pure function (no device): returns (members int32 [M], weights float32 [M] or None,
+    combine as the C ABI's integer).  The library repeats the checks that need the population's state (plane 3, the table)."""
+    if combine not in ("prob", "score"):
+        raise ValueError(f"evaluate: combine {combine!r} (\"prob\" = mean of probabilities, \"score\" = mean of scores)")
+    if plane not in (0, 3):
+        raise ValueError(f"evaluate: plane {plane!r} (0 = live parameters, 3 = kept best-epoch parameters)")
+    if int(scratch_bytes) < 0:
+        raise ValueError(f"evaluate: scratch_bytes {scratch_bytes} is negative")
+    mem = np.arange(K, dtype=np.int32) if members is None else np.ascontiguousarray(np.asarray(members, dtype=np.int64).reshape(-1))
+    if mem.size == 0:
+        raise ValueError("evaluate: no members (at least one)")
+    bad = [int(m) for m in mem if not 0 <= m < K]
+    if bad:
+        raise ValueError(f"evaluate: member {bad[0]} is outside [0, {K})")
+    w = None
+    if weights is not None:
+        w64 = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w64.size != mem.size:
+            raise ValueError(f"evaluate: {w64.size} weights for {mem.size} members")
+        if not np.all(np.isfinite(w64)) or np.any(w64 < 0):
+            raise ValueError(f"evaluate: weights must be finite and >= 0, got {w64.tolist()}")
+        if not w64.sum() > 0:
+            raise ValueError("evaluate: the weights sum to 0")
+        w = np.ascontiguousarray(w64.astype(np.float32))
+    if return_preds and loss_mode == 1:
+        raise ValueError("evaluate: return_preds with loss_mode 1 (a multi-label member has no single decision)")
+    return np.ascontiguousarray(mem.astype(np.int32)), w, 0 if combine == "prob" else 1
 
 
 def plan_population(hp: Hyper, confs: Sequence[np.ndarray], device, chunk_cols: int = 0) -> Dict[str, int]:

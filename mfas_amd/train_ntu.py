@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import torch
 
-from .engine import FeatureLoader, Population, best_dev_accuracy
+from .engine import F1_FIXED_POINT, FeatureLoader, Population, best_dev_accuracy
 from .ntu_searchable import _bump_bn_counters, _require_loader, make_order
 from .scheduler import LRCosineAnnealingScheduler
 
@@ -73,3 +73,16 @@ def test_ntu_track_acc(model, dataloaders, dataset_sizes, device=None, multitask
     _, corr = pop.forward(0, test_l.table, count=True)
     pop.close()
     return torch.tensor(corr / float(len(test_l.table)), dtype=torch.float64)
+
+
+def test_population_track_acc(pop, dataloaders, dataset_sizes, members=None, weights=None):
+    """The population form of test_ntu_track_acc (ntu.py:92-125): the accuracy of every member of `pop` (a Population) over
+    dataloaders['test'] in eval mode, and that of their weighted ensemble (mean of the members' probabilities), from ONE
+    Population.evaluate call.  Returns (float64 tensor [M] of member accuracies, 0-d float64 tensor: the ensemble's).  With
+    loss_mode 1 both are F1 'samples' averages."""
+    test_l = _require_loader(dataloaders["test"], "test", pop.device)
+    n = float(len(test_l.table))
+    res = pop.evaluate(test_l.table, members=members, weights=weights)
+    scale = 1.0 / F1_FIXED_POINT if pop.hp.loss_mode == 1 else 1.0
+    member = torch.tensor([float(c) * scale / n for c in res["member_stats"]["dev_corrects"]], dtype=torch.float64)
+    return member, torch.tensor(float(res["ensemble"]["corrects"]) * scale / n, dtype=torch.float64)
