@@ -309,6 +309,35 @@ int mfas_range_pop(void);
  * environment yields the defaults the test suites run ("hooks=0": the product library parses no test hook). */
 int mfas_tuning_describe(char* buf, int32_t cap);
 
+/* ---- The search controller's surrogate (models/search/surrogate.py:15-60, 133-157): Linear(n_in, E) + Sigmoid -> one LSTM(E, H)
+ * layer over the cells (h0 = c0 = 0, gates i, f, g, o) -> Linear(H, 1) + Sigmoid, trained with MSELoss and torch.optim.Adam.
+ * Stateless: no handle, the caller owns every buffer, the calls run on the calling thread's current device.  Parameters (and both
+ * Adam moments) are ONE flat float32 device buffer each, in state_dict order: embedding.0.weight (E x n_in), embedding.0.bias (E),
+ * lstm.weight_ih_l0 (4H x E), lstm.weight_hh_l0 (4H x H), lstm.bias_ih_l0 (4H), lstm.bias_hh_l0 (4H), hid2val.weight (1 x H),
+ * hid2val.bias (1).  MFAS_EINVAL (the message names the value; nothing is launched, no HIP call is made): n_in outside 1..8, E or H
+ * outside 16..128, L outside 1..MFAS_MAX_CELLS, n < 1, n_buckets < 1, epochs < 1, a scratch smaller than the scratch query says, a
+ * null pointer, a beta outside [0, 1), eps < 0. */
+typedef struct mfas_surrogate_shape { int32_t n_in, E, H, _pad; } mfas_surrogate_shape;
+int64_t mfas_surrogate_param_count(const mfas_surrogate_shape* shape); /* 81301 for {3, 100, 100} */
+/* Bytes of device scratch a train call needs when no bucket has more than max_L cells or max_n rows (16-byte aligned; its contents
+ * mean nothing between calls; a larger buffer changes no result). */
+int64_t mfas_surrogate_scratch_bytes(const mfas_surrogate_shape* shape, int32_t max_L, int64_t max_n);
+/* train_simple_surrogate (surrogate.py:133-157): `epochs` passes over the buckets in list order, one Adam step per bucket (two
+ * launches: the tiles' partial gradients, then their sum in tile order + Adam; no atomics, so a call is bit-reproducible), ONE
+ * synchronisation at the end for last_loss = the loss the LAST step computed, before its update.  *step: Adam steps taken so far
+ * (0 with zeroed moments for a fresh optimizer), advanced by epochs * n_buckets; a run split into several calls is bit-identical
+ * to the one-call run. */
+int mfas_surrogate_train(const mfas_surrogate_shape* shape, float* params, float* exp_avg, float* exp_avg_sq,
+                         int64_t* step /* HOST, in/out */,
+                         const float* const* x /* HOST array of DEVICE (L_b, n_b, n_in) */, const float* const* y /* ... DEVICE (n_b) */,
+                         const int32_t* L /* HOST */, const int64_t* n /* HOST */, int32_t n_buckets, int32_t epochs,
+                         double lr, double beta1, double beta2, double eps, double weight_decay,
+                         void* scratch, int64_t scratch_bytes, void* hip_stream, float* last_loss /* HOST */);
+/* The forward alone, through the same device code as the train step's: x DEVICE (L, n, n_in) -> pred DEVICE (n).  Asynchronous on
+ * hip_stream.  The forward keeps nothing outside LDS: scratch is not touched (NULL / 0 is fine). */
+int mfas_surrogate_forward(const mfas_surrogate_shape* shape, const float* params, const float* x, int32_t L, int64_t n,
+                           float* pred /* DEVICE (n) */, void* scratch, int64_t scratch_bytes, void* hip_stream);
+
 /* snapshot_best bookkeeping: a dev metric must EXCEED `threshold` to replace the kept parameters (best_acc = 0,
  * train_searchable/ntu.py:18; best_f1 = init_f1, train_searchable/mmimdb.py:18).  Default 0.  If no epoch exceeds it the
  * INITIAL parameters are restored, like the reference's best_model_sd (ntu.py:17,86). */

@@ -60,10 +60,11 @@ def parse_args(argv=None):
     p.add_argument("--engine_all_ranks", action="store_true", default=False,
                    help="under torchrun: shard every call over ALL ranks (default: only as many ranks as the calibrated step-time model "
                         "says shorten the call, mfas_amd/population.py)")
-    p.add_argument("--surrogate_device", default="cpu", choices=["cpu", "gpu"],
+    p.add_argument("--surrogate_device", default="cpu", choices=["cpu", "gpu", "engine"],
                    help="where the 81k-parameter LSTM surrogate trains (the reference puts it on its training device).  gpu: train steps "
                         "replayed as HIP graphs (0.87 ms instead of the CPU path's 1.9 ms per step; device GEMM numerics, so sampled "
-                        "configurations may differ from the CPU path's in the last digits)")
+                        "configurations may differ from the CPU path's in the last digits).  engine: the engine's own fused kernels on the "
+                        "training device, two launches per train step and one per batched prediction")
     p.add_argument("--dist_backend", default="nccl", choices=["nccl", "gloo"],
                    help="torch.distributed backend under torchrun: nccl = RCCL over xGMI (one GPU per rank); gloo lets several ranks "
                         "share one GPU (tests)")
@@ -137,7 +138,7 @@ def main(argv=None):
                                     {"train_sampled_fun": ntu.train_sampled_models,
                                      "get_layer_confs": ntu.get_possible_layer_configurations}, device)
     else:
-        data = searcher.search(surrogate_device=device if args.surrogate_device == "gpu" else "cpu")
+        data = searcher.search(surrogate_device={"gpu": device, "engine": "engine"}.get(args.surrogate_device, "cpu"))
     el = time.time() - t0
     if rank0:
         print("Search complete in {:.0f}m {:.0f}s".format(el // 60, el % 60))

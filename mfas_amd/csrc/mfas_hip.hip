@@ -16,7 +16,8 @@
 //            algorithmic minimum with state in HBM.
 // Source layout (ONE translation unit; this file includes the rest): common.hip.h (device records, helpers, LDS staging), sweep.hip.h
 // (tile_run, sweep_body, sweep_tap_body), chain.hip.h (chain_body, chain_lean, softmax / BCE rows), wide.hip.h (k_chain_wide / k_sweep_wide:
-// the batch walked in tiles), eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe); host only: plan.hip.h (the switches,
+// the batch walked in tiles), eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe), surrogate.hip.h (the search
+// controller's LSTM surrogate: k_surr_grad / k_surr_adam / k_surr_forward and their stateless C ABI); host only: plan.hip.h (the switches,
 // validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated; plan_dump.hip.h: the
 // plan as text, test-hooks variant only), launches.hip.h (the
 // launches of an epoch as data), builds.hip.h (which build a launch takes, as data: the choice functions, the builds a plan can launch, the
@@ -113,6 +114,7 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
 #include "persist.hip.h"
 #include "eval.hip.h"
 #include "pack.hip.h"
+#include "surrogate.hip.h"
 
 #include "builds.hip.h"
 #include "plan.hip.h"

@@ -118,6 +118,9 @@ class _TableSearcher(ModelSearcher):
         methods = self._methods()
         if getattr(self.args, "randsearch", False):
             return self._randsearch(self.model_type, self.dataloaders, methods, self.device)
+        if str(surrogate_device) == "engine":      # the engine's own surrogate kernels, on the training device
+            surrogate = surr.EngineSurrogate(100, 3, 100).to(self.device)
+            return self._epnas(self.model_type, {"model": surrogate, "criterion": torch.nn.MSELoss()}, self.dataloaders, methods, self.device)
         surrogate = surr.SimpleRecurrentSurrogate(100, 3, 100).to(surrogate_device)
         surrogate_dict = {"model": surrogate, "criterion": torch.nn.MSELoss()}
         # the (81k-parameter) surrogate lives where the caller wants it; the candidates train on self.device

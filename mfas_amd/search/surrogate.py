@@ -3,8 +3,12 @@
 Semantics follow /root/reference/models/search/surrogate.py: SimpleRecurrentSurrogate :15-60 (Linear(3,100)+Sigmoid
 -> LSTM(100,100) -> Linear(100,1) -> Sigmoid; Linear weights U(-0.1,0.1), biases 1.8), SurrogateDataloader :64-129
 (dict per sequence length keyed by the conf bytes, keeps the max accuracy), train_simple_surrogate :133-157.
-81,301 parameters: plain PyTorch on whatever device the caller passes (CPU is fine) — not part of the HIP hot path.
+81,301 parameters.  Three backends: plain PyTorch on the CPU (the default, the one the reference pins test), PyTorch on the device with
+the train steps replayed as HIP graphs (GraphedSurrogateTrainer), and the engine's own kernels (EngineSurrogate / EngineSurrogateTrainer:
+mfas_surrogate_train / mfas_surrogate_forward of the C ABI, two launches per train step).
 """
+import ctypes
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -179,8 +183,125 @@ class GraphedSurrogateTrainer:
         return float(last["loss_live"].item())
 
 
+_STATE_ORDER = ("embedding.0.weight", "embedding.0.bias", "lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_hh_l0",
+                "hid2val.weight", "hid2val.bias")
+
+
+class EngineSurrogate(SimpleRecurrentSurrogate):
+    """SimpleRecurrentSurrogate whose no_grad forward on a HIP tensor is ONE launch of the engine (mfas_surrogate_forward) and whose
+    training is the engine's (EngineSurrogateTrainer).  Same constructor, same nn.Parameters, same initialisation draws: state_dicts are
+    interchangeable with the CPU module's.  The engine reads a flat device copy of the parameters in state_dict order; the copy is
+    refreshed whenever a parameter tensor has changed since it was made.  With grad enabled (or on a CPU tensor) the forward is the
+    parent's PyTorch one: this module adds no autograd edge of its own."""
+
+    def __init__(self, num_hidden=100, number_input_feats=3, size_ebedding=100):
+        super().__init__(num_hidden, number_input_feats, size_ebedding)
+        from .. import _lib
+        self._shape = _lib.mfas_surrogate_shape(number_input_feats, size_ebedding, num_hidden, 0)
+        self._flat = None
+        self._flat_of = None
+
+    def _ordered(self):
+        named = dict(self.named_parameters())
+        return [named[k] for k in _STATE_ORDER]
+
+    def _marks(self):
+        return [(p.data_ptr(), p._version) for p in self._ordered()]
+
+    def flat_parameters(self):
+        """The flat float32 device copy of the parameters (state_dict order), refreshed if a parameter changed since the last call."""
+        ps = self._ordered()
+        if ps[0].device.type != "cuda":
+            raise RuntimeError("EngineSurrogate: the engine runs on a HIP device (module is on %s)" % ps[0].device)
+        marks = self._marks()
+        if self._flat is None or self._flat.device != ps[0].device or self._flat_of != marks:
+            with torch.no_grad():
+                self._flat = torch.cat([p.detach().reshape(-1).float() for p in ps]).contiguous()
+            self._flat_of = marks
+        return self._flat
+
+    def adopt_flat(self):
+        """Write the flat copy (just trained by the engine) back into the nn.Parameters."""
+        with torch.no_grad():
+            off = 0
+            for p in self._ordered():
+                p.copy_(self._flat[off:off + p.numel()].view_as(p))
+                off += p.numel()
+        self._flat_of = self._marks()
+
+    def forward(self, sequence_of_operations):
+        x = sequence_of_operations
+        if not x.is_cuda or torch.is_grad_enabled():
+            return super().forward(x)
+        from .. import _lib
+        x = x.detach().float().contiguous()
+        L, n = int(x.shape[0]), int(x.shape[1])
+        flat = self.flat_parameters()
+        pred = torch.empty(n, 1, device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().mfas_surrogate_forward(ctypes.byref(self._shape), flat.data_ptr(), x.data_ptr(), L, n, pred.data_ptr(),
+                                                         None, 0, torch.cuda.current_stream(x.device).cuda_stream))
+        return pred
+
+
+class EngineSurrogateTrainer:
+    """train_simple_surrogate through the engine: the buckets are uploaded, mfas_surrogate_train runs every epoch's steps (two launches
+    each) with one synchronisation at the end, and the parameters go back into the module's nn.Parameters.  Owns Adam's exp_avg /
+    exp_avg_sq, the step count and the scratch; lr / betas / eps / weight_decay are read from optimizer.param_groups[0] at every call
+    (the torch optimizer's own state is not used)."""
+
+    def __init__(self, model, optimizer):
+        g = optimizer.param_groups[0]
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError("EngineSurrogateTrainer: amsgrad / maximize are not supported by the engine's Adam")
+        self.model, self.opt = model, optimizer
+        flat = model.flat_parameters()
+        self.exp_avg = torch.zeros_like(flat)
+        self.exp_avg_sq = torch.zeros_like(flat)
+        self.step = ctypes.c_int64(0)
+        self.scratch = None
+
+    def train(self, data_tensors, num_epochs):
+        from .. import _lib
+        L_ = _lib.lib()
+        m = self.model
+        flat = m.flat_parameters()
+        dev = flat.device
+        xs = [x.to(dev, torch.float32).contiguous() for x in data_tensors[0]]
+        ys = [y.to(dev, torch.float32).reshape(-1).contiguous() for y in data_tensors[1]]
+        nb = len(xs)
+        Ls = (ctypes.c_int32 * nb)(*[int(x.shape[0]) for x in xs])
+        ns = (ctypes.c_int64 * nb)(*[int(x.shape[1]) for x in xs])
+        need = L_.mfas_surrogate_scratch_bytes(ctypes.byref(m._shape), max(Ls), max(ns)) if nb else 0
+        if need < 0:
+            _lib.check(int(need))
+        if self.scratch is None or self.scratch.numel() < need or self.scratch.device != dev:
+            self.scratch = torch.empty(int(need), dtype=torch.uint8, device=dev)
+        g = self.opt.param_groups[0]
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError("EngineSurrogateTrainer: amsgrad / maximize are not supported by the engine's Adam")
+        xp = (ctypes.c_void_p * nb)(*[x.data_ptr() for x in xs])
+        yp = (ctypes.c_void_p * nb)(*[y.data_ptr() for y in ys])
+        loss = ctypes.c_float(0.0)
+        with torch.cuda.device(dev):
+            _lib.check(L_.mfas_surrogate_train(ctypes.byref(m._shape), flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                               ctypes.byref(self.step), xp, yp, Ls, ns, nb, int(num_epochs), float(g["lr"]),
+                                               float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                                               self.scratch.data_ptr(), self.scratch.numel(), torch.cuda.current_stream(dev).cuda_stream,
+                                               ctypes.byref(loss)))
+        m.adopt_flat()
+        m.train(False)
+        return float(loss.value)
+
+
 def train_simple_surrogate(model, criterion, optimizer, data_tensors, num_epochs, device):
     """surrogate.py:133-157: ``num_epochs`` passes over the buckets, one optimizer step per bucket; returns the last loss."""
+    if isinstance(model, EngineSurrogate) and isinstance(criterion, nn.MSELoss):
+        tr = getattr(model, "_engine_trainer", None)
+        if tr is None or tr.opt is not optimizer:
+            tr = EngineSurrogateTrainer(model, optimizer)
+            model._engine_trainer = tr
+        return tr.train(data_tensors, num_epochs)
     if torch.device(device).type == "cuda" and isinstance(criterion, nn.MSELoss):
         tr = getattr(model, "_graphed_trainer", None)
         if tr is None or tr.opt is not optimizer:
