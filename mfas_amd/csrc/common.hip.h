@@ -328,10 +328,11 @@ __device__ __forceinline__ int64_t tile_addr(int64_t seg_off, int rows_p, int cc
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void stage_table(float* dst, int stride, const void* tab, int dtype, int width,
                                             int col0, int ncols, const int32_t* ord, int64_t pos,
-                                            int base, int nvalid, int nrows, int tid, int nthreads) {
+                                            int base, int nvalid, int nrows, int tid, int nthreads, int first = 0) {
+    // first: elements the caller has staged already (the two-halves form below took the first pass: first = nthreads)
     if (dtype == MFAS_DT_F32) {
         const int vpr = ncols >> 2;
-        for (int e = tid; e < nrows * vpr; e += nthreads) {
+        for (int e = tid + first; e < nrows * vpr; e += nthreads) {
             const int b = e / vpr, c = (e - b * vpr) << 2;
             f32x4 val = {0.f, 0.f, 0.f, 0.f};
             if (b < nvalid) {
@@ -342,7 +343,7 @@ __device__ __forceinline__ void stage_table(float* dst, int stride, const void* 
         }
     } else {
         const int vpr = ncols >> 3;
-        for (int e = tid; e < nrows * vpr; e += nthreads) {
+        for (int e = tid + first; e < nrows * vpr; e += nthreads) {
             const int b = e / vpr, c = (e - b * vpr) << 3;
             f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
             if (b < nvalid) {
@@ -414,12 +415,70 @@ __device__ __forceinline__ float ldc1(const float* p) {
 // f32 row-major global base[idx0 + b * src_stride + c] -> LDS [nrows][stride]
 template <bool COH>
 __device__ __forceinline__ void stage_f32(float* dst, int stride, const float* base, int64_t idx0, int src_stride, int ncols,
-                                          int nrows, int tid, int nthreads) {
+                                          int nrows, int tid, int nthreads, int first = 0) {
     const int vpr = ncols >> 2;
-    for (int e = tid; e < nrows * vpr; e += nthreads) {
+    for (int e = tid + first; e < nrows * vpr; e += nthreads) {
         const int b = e / vpr, c = (e - b * vpr) << 2;
         *reinterpret_cast<f32x4*>(dst + b * stride + c) = ldc4<COH>(base, idx0 + (int64_t)b * src_stride + c);
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Staging in two halves (sweep.hip.h, sweep_body): stage_table / stage_f32 are a loop of load -> wait -> LDS write per stream, so a unit
+// that stages five streams pays five memory round trips one after another.  The ISSUE half (stage_issue) requests a stream's FIRST pass
+// (element e = tid: 16 bytes per thread) into registers and waits for nothing; the COMMIT half writes the LDS exactly as the loop's first
+// pass does — the same values, the same zero rows for b >= nvalid (a lane that loads nothing holds zeros, which every dtype converts to
+// +0.0f).  Several issue halves in a row are one round trip.  What a stream has beyond nthreads elements goes through the loops (first =
+// nthreads).
+// ------------------------------------------------------------------------------------------------
+// the table row this lane's element of the first pass comes from; -1: the lane loads nothing (stream off, past the tile, a padding row)
+__device__ __forceinline__ int64_t stage_table_row(bool on, int dtype, int ncols, const int32_t* ord, int64_t pos, int base, int nvalid,
+                                                   int nrows, int tid) {
+    const int vpr = ncols >> (dtype == MFAS_DT_F32 ? 2 : 3), b = tid / vpr;
+    if (!on || tid >= nrows * vpr || b >= nvalid) return -1;
+    return ord ? (int64_t)ord[pos + b] : (int64_t)(base + b);
+}
+// where this lane's 16 bytes of the first pass lie (meaningless for row < 0)
+__device__ __forceinline__ const char* stage_table_src(const void* tab, int dtype, int width, int col0, int ncols, int64_t row, int tid) {
+    const int sh = dtype == MFAS_DT_F32 ? 2 : 3, vpr = ncols >> sh, b = tid / vpr, c = (tid - b * vpr) << sh;
+    return reinterpret_cast<const char*>(tab) + ((row * width + col0 + c) << (dtype == MFAS_DT_F32 ? 2 : 1));
+}
+// the request: made by EVERY lane on every path (no branch around a load).  A lane with nothing to fetch reads `idle` (16 readable
+// bytes) and holds zeros.
+__device__ __forceinline__ u32x4 stage_issue(bool mine, const char* src, const void* idle) {
+    const u32x4 raw = *reinterpret_cast<const u32x4*>(mine ? src : reinterpret_cast<const char*>(idle));
+    return mine ? raw : (u32x4){0u, 0u, 0u, 0u};
+}
+__device__ __forceinline__ void stage_table_commit(bool on, float* dst, int stride, int dtype, int ncols, int nrows, int tid, const u32x4 raw) {
+    const int sh = dtype == MFAS_DT_F32 ? 2 : 3, vpr = ncols >> sh, b = tid / vpr, c = (tid - b * vpr) << sh;
+    if (!on || tid >= nrows * vpr) return;
+    if (dtype == MFAS_DT_F32) {
+        *as_lds(reinterpret_cast<f32x4*>(dst + b * stride + c)) = __builtin_bit_cast(f32x4, raw);
+    } else {
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (dtype == MFAS_DT_BF16) {
+                f[2 * j] = __uint_as_float(raw[j] << 16);
+                f[2 * j + 1] = __uint_as_float(raw[j] & 0xFFFF0000U);
+            } else {
+                f[2 * j] = __half2float(__ushort_as_half((unsigned short)(raw[j] & 0xFFFFU)));
+                f[2 * j + 1] = __half2float(__ushort_as_half((unsigned short)(raw[j] >> 16)));
+            }
+        }
+        *as_lds(reinterpret_cast<f32x4*>(dst + b * stride + c)) = (f32x4){f[0], f[1], f[2], f[3]};
+        *as_lds(reinterpret_cast<f32x4*>(dst + b * stride + c + 4)) = (f32x4){f[4], f[5], f[6], f[7]};
+    }
+}
+// the same for stage_f32<false> (plain loads): stage_issue(stage_f32_mine(..), stage_f32_src(..), idle), then stage_f32_commit
+__device__ __forceinline__ bool stage_f32_mine(bool on, int ncols, int nrows, int tid) { return on && tid < nrows * (ncols >> 2); }
+__device__ __forceinline__ const char* stage_f32_src(const float* base, int64_t idx0, int src_stride, int ncols, int tid) {
+    const int vpr = ncols >> 2, b = tid / vpr, c = (tid - b * vpr) << 2;
+    return reinterpret_cast<const char*>(base + idx0 + (int64_t)b * src_stride + c);
+}
+__device__ __forceinline__ void stage_f32_commit(bool on, float* dst, int stride, int ncols, int nrows, int tid, const u32x4 raw) {
+    const int vpr = ncols >> 2, b = tid / vpr, c = (tid - b * vpr) << 2;
+    if (on && tid < nrows * vpr) *as_lds(reinterpret_cast<f32x4*>(dst + b * stride + c)) = __builtin_bit_cast(f32x4, raw);
 }
 
 // U = tiles of W/m/v in flight per wave (x3 planes).  A workgroup has 2 waves per SIMD, so two workgroups share a CU only

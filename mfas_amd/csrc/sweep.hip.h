@@ -278,6 +278,55 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& 
     const int64_t sbo = cd.step_off;   // this candidate's step buffers inside a.stepbuf
     const bool red = a.red_cnt != nullptr;
 
+    // ---- the k_step builds: a unit's staged streams are requested TOGETHER (common.hip.h, staging in two halves: the first pass of every
+    // stream, 512 threads x 16 bytes, which is the whole stream of an MB = 1 unit), then written to the LDS, then the streams' remainders go
+    // through the loops.  The loops alone are a load -> wait -> LDS write chain per stream, one memory round trip after another: 3 for a plain
+    // or virtual pass (x_t, x_{t+1}, dy), 5 for a double pass (x_{t-1}, dy_{t-1} as well), against 1 here.  Only the sample order's entries (a
+    // unit that stages from the table through `ord`) are a round trip of their own in front of the row loads.  Every request is made by every
+    // lane: one with nothing to fetch reads `idle`, 16 bytes of the unit's own descriptor, and holds zeros — the zero rows of b >= nvalid.
+    // Not in this form: the same-group builds (they wait for their cell's flag between the rows and dy), and k_step<2, NT, 4, 0, 1>, whose
+    // 128 registers the walk fills (the two-halves form costs it 7 spilled VGPRs); requesting the first W / m / v tiles here too spilled
+    // in every build with a double walk (profiles/sweep_prologue_ab.log).
+    constexpr bool BATCHED = !COH && !(MB == 2 && U == 1 && DEFER);
+    if constexpr (BATCHED) {
+        const int dt = a.tab.dtype;
+        const bool gath = a.gather && feat;      // the candidate's rows were gathered a launch ago (gather_body): rows 0 .. B-1 of its own copy
+        const char* tp = feat ? reinterpret_cast<const char*>(d.kind == KIND_S ? a.tab.s[d.tap] : a.tab.v[d.tap]) : nullptr;
+        const char *sp = tp, *sc = tp, *sn = tp;     // where the rows of batch t - 1 / t / t + 1 are read from
+        if (gath) {
+            const char* gb = a.gather + (int64_t)cd.gidx * a.g_cand_stride + gather_tap_off(a.g, d.kind, d.tap, dt == MFAS_DT_F32 ? 4 : 2);
+            sp = gb + (int64_t)a.g_par_p * a.g_par_stride; sc = gb + (int64_t)a.g_par_t * a.g_par_stride; sn = gb + (int64_t)a.g_par_n * a.g_par_stride;
+        }
+        const int32_t* ordp = gath ? nullptr : cand_order(a.order, a.g, cd.gidx);
+        const bool on_p = dbl, on_t = upd && feat, on_n = fwd, on_o = upd && !feat;
+        const int64_t row_p = stage_table_row(on_p, dt, cc, ordp, a.pos_p, gath ? 0 : a.base_p, a.nvalid_p, Bp, tid);
+        const int64_t row_t = stage_table_row(on_t, dt, cc, ordp, st.pos_t, gath ? 0 : st.base_t, st.nvalid_t, Bp, tid);
+        const int64_t row_n = stage_table_row(on_n, dt, cc, ordp, st.pos_n, gath ? 0 : st.base_n, st.nvalid_n, Bp, tid);
+        // dy of this unit's rows: columns [16*rb0, 16*rb0 + rows_p) of the segment's dy (row stride = the segment's padded rows)
+        const int64_t dsrc = (d.kind == KIND_HEAD ? sbo + a.g.sb_dlog : sbo + a.g.sb_dy + (int64_t)d.cell * Bp * a.g.Rp) + d.rb0 * 16;
+        const int64_t dsrc_p = sbo + a.sb_dy_prev + (int64_t)d.cell * Bp * a.g.Rp + d.rb0 * 16;
+        const int64_t osrc = sbo + a.g.sb_xo + (int64_t)(d.kind == KIND_OUT ? d.cell - 1 : cd.L - 1) * Bp * a.g.Rp + d.k0;      // OUT / HEAD: x_t = `out`
+        const void* idle = a.desc + bid;
+        const u32x4 q_dy = stage_issue(stage_f32_mine(upd, rows_p, Bp, tid), stage_f32_src(a.stepbuf, dsrc, d.seg_nrb * 16, rows_p, tid), idle);
+        const u32x4 q_dyp = stage_issue(stage_f32_mine(dbl, rows_p, Bp, tid), stage_f32_src(a.stepbuf, dsrc_p, d.seg_nrb * 16, rows_p, tid), idle);
+        const u32x4 q_p = stage_issue(row_p >= 0, stage_table_src(sp, dt, d.width, d.k0, cc, row_p, tid), idle);
+        const u32x4 q_t = stage_issue(on_o ? stage_f32_mine(true, cc, Bp, tid) : row_t >= 0,
+                                      on_o ? stage_f32_src(a.stepbuf, osrc, a.g.Rp, cc, tid) : stage_table_src(sc, dt, d.width, d.k0, cc, row_t, tid), idle);
+        const u32x4 q_n = stage_issue(row_n >= 0, stage_table_src(sn, dt, d.width, d.k0, cc, row_n, tid), idle);
+        stage_f32_commit(upd, dyl, SD, rows_p, Bp, tid, q_dy);
+        stage_f32_commit(dbl, dyp, SD, rows_p, Bp, tid, q_dyp);
+        stage_table_commit(on_p, xp, ST, dt, cc, Bp, tid, q_p);
+        if (on_o) stage_f32_commit(true, xt, ST, cc, Bp, tid, q_t);
+        else stage_table_commit(on_t, xt, ST, dt, cc, Bp, tid, q_t);
+        stage_table_commit(on_n, xn, SN, dt, cc, Bp, tid, q_n);
+        // what a stream has beyond one pass (MB = 2 / 4, a wide chunk)
+        if (on_p) stage_table(xp, ST, sp, dt, d.width, d.k0, cc, ordp, a.pos_p, gath ? 0 : a.base_p, a.nvalid_p, Bp, tid, STEP_THREADS, STEP_THREADS);
+        if (on_t) stage_table(xt, ST, sc, dt, d.width, d.k0, cc, ordp, st.pos_t, gath ? 0 : st.base_t, st.nvalid_t, Bp, tid, STEP_THREADS, STEP_THREADS);
+        if (on_n) stage_table(xn, SN, sn, dt, d.width, d.k0, cc, ordp, st.pos_n, gath ? 0 : st.base_n, st.nvalid_n, Bp, tid, STEP_THREADS, STEP_THREADS);
+        if (on_o) stage_f32<false>(xt, ST, a.stepbuf, osrc, a.g.Rp, cc, Bp, tid, STEP_THREADS, STEP_THREADS);
+        if (upd) stage_f32<false>(dyl, SD, a.stepbuf, dsrc, d.seg_nrb * 16, rows_p, Bp, tid, STEP_THREADS, STEP_THREADS);
+        if (dbl) stage_f32<false>(dyp, SD, a.stepbuf, dsrc_p, d.seg_nrb * 16, rows_p, Bp, tid, STEP_THREADS, STEP_THREADS);
+    } else {
     if (!COH && a.gather && feat) {      // the candidate's rows were gathered a launch ago (gather_body): rows 0 .. B-1 of its own copy
         const char* gb = a.gather + (int64_t)cd.gidx * a.g_cand_stride + gather_tap_off(a.g, d.kind, d.tap, a.tab.dtype == MFAS_DT_F32 ? 4 : 2);
         if (dbl) stage_table(xp, ST, gb + (int64_t)a.g_par_p * a.g_par_stride, a.tab.dtype, d.width, d.k0, cc, nullptr, 0, 0, a.nvalid_p, Bp, tid, STEP_THREADS);
@@ -328,6 +377,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a, const SweepStep& 
         const int64_t dsrc = d.kind == KIND_HEAD ? sbo + a.g.sb_dlog : sbo + a.g.sb_dy + (int64_t)d.cell * Bp * a.g.Rp;
         stage_f32<COH>(dyl, SD, a.stepbuf, dsrc + d.rb0 * 16, d.seg_nrb * 16, rows_p, Bp, tid, STEP_THREADS);
         if (dbl) stage_f32<false>(dyp, SD, a.stepbuf, sbo + a.sb_dy_prev + (int64_t)d.cell * Bp * a.g.Rp + d.rb0 * 16, d.seg_nrb * 16, rows_p, Bp, tid, STEP_THREADS);
+    }
     }
     __syncthreads();
     SW_UNIT_STAMP(1);
