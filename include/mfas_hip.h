@@ -223,6 +223,27 @@ int mfas_population_evaluate(mfas_population* pop, const mfas_table* tab, int32_
                              mfas_epoch_stats* member_stats, int32_t* member_preds, float* scores,
                              mfas_epoch_stats* ensemble_stats);
 
+/* mfas_population_evaluate with a per-class report: the same twelve parameters, unchanged in order and meaning, then three DEVICE
+ * arrays, any of which may be NULL.  Slot s of an array is member s of the list for s < M and the ensemble for s = M.
+ *   confusion:    int64 [(M+1)][C][C], loss_mode 0 only: [s][t][q] = the rows with label t that slot s decided as q (a member's
+ *                 decision is member_preds' bit for bit, the ensemble's the first maximum of `scores`; a NaN in class 0 decides 0).
+ *   rank_hist:    int64 [(M+1)][C], loss_mode 0 only: [s][r] = the rows whose label has rank r in slot s's score row (a member's
+ *                 score row, the ensemble's probabilities).  The rank is the number of classes that precede the label in the order
+ *                 "score descending, NaN last, equal scores by lower class first"; its running sum up to k-1 is the top-k count.
+ *                 Rank 0 coincides with "decided correctly" on every row whose class-0 score is not NaN.
+ *   label_counts: int64 [(M+1)][C][3], loss_mode 1 only: per class (true positives, predicted positives, actual positives); a
+ *                 member predicts a class when sigmoid(z) > f1_threshold, the ensemble when its probability does, and a class is
+ *                 actual when multilabel > 0.5.
+ * The call zeroes the arrays it was given on the population's stream, then adds integers only: the arrays depend neither on the run
+ * nor on scratch_bytes.  Every other output is bit-identical to mfas_population_evaluate's, and with all three NULL the call IS that
+ * one.  MFAS_EINVAL, naming the argument, nothing changed: confusion or rank_hist with loss_mode 1; label_counts with loss_mode 0;
+ * a report of more than 65534 members; everything mfas_population_evaluate refuses. */
+int mfas_population_evaluate_report(mfas_population* pop, const mfas_table* tab, int32_t plane, const int32_t* members,
+                                    const float* weights, int32_t M, int32_t combine, int64_t scratch_bytes,
+                                    mfas_epoch_stats* member_stats, int32_t* member_preds, float* scores,
+                                    mfas_epoch_stats* ensemble_stats, int64_t* confusion, int64_t* rank_hist,
+                                    int64_t* label_counts);
+
 /* Replaces Searchable_Skeleton_Image_Net.forward in TRAIN mode (ntu_searchable.py:206-247 with model.train(True)) for
  * candidate k on ONE batch = rows [row0, row0+nrows) of a table, nrows <= hyper.B: batch-statistics BatchNorm (the running
  * statistics are updated, as any train-mode forward does), dropout from the candidate's stream at `step_index`; writes

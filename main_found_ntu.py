@@ -51,6 +51,9 @@ def parse_args(argv=None):
                         "(mean of the members' probabilities).  The members are trained on the single-phase SEARCH schedule "
                         "(train_sampled_models: --epochs epochs, one Adam, no phase-1 pretraining), not the two-phase schedule of "
                         "--conf.  Needs --no-multitask (the search-mode train loop refuses multitask); single process only.")
+    p.add_argument("--report", action="store_true", default=False,
+                   help="with --ensemble: also print top-1 / top-5 and the five worst classes of every member and of the ensemble "
+                        "(Population.evaluate(report=True): the confusion matrix and the label's rank from the same call)")
     args = p.parse_args(argv)
     if args.ensemble is not None and args.multitask:
         p.error("--ensemble needs --no-multitask: the search-mode train loop refuses multitask")
@@ -69,7 +72,7 @@ def train_ensemble(args, loaders, device):
         for k, m in enumerate(models):
             pop.set_params(k, m.flat_params())
         sizes = {x: len(loaders[x].dataset) for x in ("train", "test", "dev")}
-        member, ens = M.test_population_track_acc(pop, loaders, sizes)
+        member, ens = M.test_population_track_acc(pop, loaders, sizes, report=args.report)
     finally:
         pop.close()
     for c, a in zip(args.ensemble, member.tolist()):

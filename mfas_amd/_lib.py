@@ -86,6 +86,7 @@ def lib():
     L.mfas_population_move.argtypes = [P, C.c_int32, P, C.c_int32]
     L.mfas_population_launch_record.argtypes = [P, C.c_char_p, C.c_int32]
     L.mfas_population_evaluate.argtypes = [P, C.POINTER(mfas_table), C.c_int32, P, P, C.c_int32, C.c_int32, C.c_int64, P, P, P, P]
+    L.mfas_population_evaluate_report.argtypes = L.mfas_population_evaluate.argtypes + [P, P, P]
     S = C.POINTER(mfas_surrogate_shape)
     L.mfas_surrogate_param_count.argtypes = [S]
     L.mfas_surrogate_param_count.restype = C.c_int64
@@ -105,7 +106,7 @@ EXPORTS = ["mfas_last_error", "mfas_version", "mfas_population_create", "mfas_po
            "mfas_population_set_best_threshold", "mfas_population_forward_train", "mfas_population_schedule",
            "mfas_population_plan", "mfas_population_backward", "mfas_range_push", "mfas_range_pop", "mfas_population_init_torch_streams", "mfas_tuning_describe",
            "mfas_population_train_from", "mfas_population_set_state", "mfas_population_get_progress", "mfas_population_set_progress",
-           "mfas_population_move", "mfas_population_launch_record", "mfas_population_evaluate",
+           "mfas_population_move", "mfas_population_launch_record", "mfas_population_evaluate", "mfas_population_evaluate_report",
            "mfas_surrogate_param_count", "mfas_surrogate_scratch_bytes", "mfas_surrogate_train", "mfas_surrogate_forward"]
 
 

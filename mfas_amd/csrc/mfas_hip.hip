@@ -22,7 +22,8 @@
 // plan as text, test-hooks variant only), launches.hip.h (the
 // launches of an epoch as data), builds.hip.h (which build a launch takes, as data: the choice functions, the builds a plan can launch, the
 // tables' row lists), state.hip.h (state in and out, the candidate carry, move, the fallback), train.hip.h (the train call); vote.hip.h (k_vote and the host side of
-// mfas_population_evaluate: members through k_eval, then the vote).  Here:
+// mfas_population_evaluate: members through k_eval, then the vote), tally.hip.h (k_tally: the per-class tallies of
+// mfas_population_evaluate_report).  Here:
 // k_step / k_chain, the kernel tables (key -> instantiation: the only place one is named), create / destroy, the C ABI.
 // Dev evaluation is row-parallel (k_eval).  Weights live in a 16x16 tile-major layout that is exactly the
 // MFMA 16x16x4 f32 operand layout, so every W/m/v access is one coalesced 16 B/lane load.
@@ -515,6 +516,7 @@ static hipError_t launch_eval(mfas_population* p, const EvalArgs& a, int ncand, 
 #include "state.hip.h"
 #include "train.hip.h"
 #include "vote.hip.h"
+#include "tally.hip.h"
 
 extern "C" int mfas_population_set_params(mfas_population* p, int32_t k, const float* flat) {
     if (!p || !flat || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad argument");
@@ -630,7 +632,17 @@ extern "C" int mfas_population_evaluate(mfas_population* p, const mfas_table* ta
                                         const float* weights, int32_t M, int32_t combine, int64_t scratch_bytes,
                                         mfas_epoch_stats* member_stats, int32_t* member_preds, float* scores,
                                         mfas_epoch_stats* ensemble_stats) {
-    return evaluate_impl(p, tab, plane, members, weights, M, combine, scratch_bytes, member_stats, member_preds, scores, ensemble_stats);
+    return evaluate_impl(p, tab, plane, members, weights, M, combine, scratch_bytes, member_stats, member_preds, scores, ensemble_stats,
+                         nullptr, nullptr, nullptr);
+}
+
+extern "C" int mfas_population_evaluate_report(mfas_population* p, const mfas_table* tab, int32_t plane, const int32_t* members,
+                                               const float* weights, int32_t M, int32_t combine, int64_t scratch_bytes,
+                                               mfas_epoch_stats* member_stats, int32_t* member_preds, float* scores,
+                                               mfas_epoch_stats* ensemble_stats, int64_t* confusion, int64_t* rank_hist,
+                                               int64_t* label_counts) {
+    return evaluate_impl(p, tab, plane, members, weights, M, combine, scratch_bytes, member_stats, member_preds, scores, ensemble_stats,
+                         confusion, rank_hist, label_counts);
 }
 
 extern "C" int mfas_population_forward_train(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0, int32_t nrows,

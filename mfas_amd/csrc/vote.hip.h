@@ -200,13 +200,17 @@ __global__ void __launch_bounds__(256) k_vote_loss(const float* row_loss, const 
 // Host side of mfas_population_evaluate: every check first (a refused call changes nothing), then per row block one k_eval launch
 // per member (ncand = 1, the path mfas_population_forward takes; its statistics go to the call's own slots) and one k_vote.
 // Everything the call writes on the device lies in the population's evaluate arena (grow-only, read by nothing else) or in the
-// caller's output buffers.
+// caller's output buffers.  With any of confusion / rank_hist / label_counts (mfas_population_evaluate_report) every row block's
+// k_vote is followed by one k_tally (tally.hip.h); with none of them the call launches, clears and allocates what it always did.
 // ------------------------------------------------------------------------------------------------
 static size_t vote_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
+// k_tally's launch for one row block (tally.hip.h): the per-class tallies of mfas_population_evaluate_report
+static hipError_t tally_block(const VoteArgs& va, int64_t* confusion, int64_t* rank_hist, int64_t* label_counts, int lpr, hipStream_t st);
+
 static int evaluate_impl(mfas_population* p, const mfas_table* tab, int32_t plane, const int32_t* members, const float* weights,
                          int32_t M, int32_t combine, int64_t scratch_bytes, mfas_epoch_stats* member_stats, int32_t* member_preds,
-                         float* scores, mfas_epoch_stats* ensemble_stats) {
+                         float* scores, mfas_epoch_stats* ensemble_stats, int64_t* confusion, int64_t* rank_hist, int64_t* label_counts) {
     if (!p) return fail(MFAS_EINVAL, "evaluate: null population");
     const Geo& g = p->plan.g;
     if (M <= 0) return fail(MFAS_EINVAL, "evaluate: M = " + std::to_string(M) + " members (at least one)");
@@ -236,6 +240,11 @@ static int evaluate_impl(mfas_population* p, const mfas_table* tab, int32_t plan
         for (int m = 0; m < M; ++m) wn[m] = (float)((double)weights[m] / sum);
     }
     if (member_preds && g.loss_mode == 1) return fail(MFAS_EINVAL, "evaluate: member_preds with loss_mode 1 (a multi-label member has no single decision)");
+    if (confusion && g.loss_mode == 1) return fail(MFAS_EINVAL, "evaluate: confusion with loss_mode 1 (a multi-label member has no single decision)");
+    if (rank_hist && g.loss_mode == 1) return fail(MFAS_EINVAL, "evaluate: rank_hist with loss_mode 1 (a multi-label row has no single label to rank)");
+    if (label_counts && g.loss_mode == 0) return fail(MFAS_EINVAL, "evaluate: label_counts with loss_mode 0 (per-class positives belong to the multi-label head)");
+    const bool report = confusion || rank_hist || label_counts;
+    if (report && M >= 65535) return fail(MFAS_EINVAL, "evaluate: a report of M = " + std::to_string(M) + " members (at most 65534: one grid row per slot)");
     if (int rc = check_table(p, tab, g.multitask)) return rc;
     const int64_t N = tab->N, row_bytes = (int64_t)M * g.C * 4;
     if (scratch_bytes == 0) scratch_bytes = (int64_t)64 << 20;
@@ -250,10 +259,11 @@ static int evaluate_impl(mfas_population* p, const mfas_table* tab, int32_t plan
 
     HIPCHK(hipSetDevice(p->device));
     hipStream_t st = p->stream;
-    // the arena: weights | member statistics | ensemble result | row losses | logits scratch
+    // the arena: weights | member statistics | ensemble result | row losses | logits scratch | (a report without the caller's scores:) scores
     const size_t o_w = 0, o_st = o_w + vote_align(sizeof(float) * M), o_out = o_st + vote_align(sizeof(DevStats) * M),
                  o_rl = o_out + vote_align(sizeof(VoteOut)), o_lg = o_rl + vote_align(sizeof(float) * (size_t)N),
-                 need = o_lg + vote_align((size_t)brows * (size_t)row_bytes);
+                 o_sc = o_lg + vote_align((size_t)brows * (size_t)row_bytes),
+                 need = o_sc + ((report && !scores) ? vote_align(sizeof(float) * (size_t)N * (size_t)g.C) : 0);
     if (p->vote_cap < need) {
         HIPCHK(hipFree(p->d_vote));
         p->d_vote = nullptr; p->vote_cap = 0;
@@ -268,6 +278,10 @@ static int evaluate_impl(mfas_population* p, const mfas_table* tab, int32_t plan
     float* d_lg = reinterpret_cast<float*>(p->d_vote + o_lg);
     HIPCHK(hipMemcpyAsync(d_w, wn.data(), sizeof(float) * M, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(p->d_vote + o_st, 0, o_rl - o_st, st));
+    const size_t slots = (size_t)M + 1, nc = (size_t)g.C;
+    if (confusion) HIPCHK(hipMemsetAsync(confusion, 0, sizeof(int64_t) * slots * nc * nc, st));
+    if (rank_hist) HIPCHK(hipMemsetAsync(rank_hist, 0, sizeof(int64_t) * slots * nc, st));
+    if (label_counts) HIPCHK(hipMemsetAsync(label_counts, 0, sizeof(int64_t) * slots * nc * 3, st));
 
     EvalArgs ea;
     memset(&ea, 0, sizeof(ea));
@@ -276,7 +290,7 @@ static int evaluate_impl(mfas_population* p, const mfas_table* tab, int32_t plan
     memset(&va, 0, sizeof(va));
     va.logits = d_lg; va.weights = d_w; va.label = tab->label; va.vlogit = tab->vlogit; va.slogit = tab->slogit; va.multilabel = tab->multilabel;
     va.pos_w = p->d_posw; va.N = N; va.M = M; va.C = g.C; va.loss_mode = g.loss_mode; va.multitask = g.multitask; va.combine = combine;
-    va.f1_th = g.f1_th; va.member_preds = member_preds; va.scores = scores; va.row_loss = d_rl; va.corr = &d_out->corr;
+    va.f1_th = g.f1_th; va.member_preds = member_preds; va.scores = (report && !scores) ? reinterpret_cast<float*>(p->d_vote + o_sc) : scores; va.row_loss = d_rl; va.corr = &d_out->corr;
     for (int64_t row0 = 0; row0 < N; row0 += brows) {
         const int64_t rows = std::min(brows, N - row0);
         for (int m = 0; m < M; ++m) {
@@ -291,6 +305,7 @@ static int evaluate_impl(mfas_population* p, const mfas_table* tab, int32_t plan
         else if (lpr == 32) hipLaunchKernelGGL(k_vote<32>, dim3(grid), dim3(256), 0, st, va);
         else hipLaunchKernelGGL(k_vote<64>, dim3(grid), dim3(256), 0, st, va);
         HIPCHK(hipGetLastError());
+        if (report) HIPCHK(tally_block(va, confusion, rank_hist, label_counts, lpr, st));
     }
     hipLaunchKernelGGL(k_vote_loss, dim3(1), dim3(256), 0, st, (const float*)d_rl, N, &d_out->loss);
     HIPCHK(hipGetLastError());

@@ -480,13 +480,17 @@ class Population:
 
     def evaluate(self, table: FeatureTable, members: Optional[Sequence[int]] = None, weights: Optional[Sequence[float]] = None,
                  plane: int = 0, combine: str = "prob", scratch_bytes: int = 0, return_scores: bool = False,
-                 return_preds: bool = False):
+                 return_preds: bool = False, report: bool = False):
         """Score `members` (candidate indices, repeats allowed; None = all K) on every row of `table`, one by one and as a weighted
         ensemble, in one call (mfas_population_evaluate).  Every member runs the dev pass's eval-mode forward; combine "prob" averages
         the members' probabilities, "score" their score rows; plane 3 evaluates the kept best-epoch parameters of an unfinished
         snapshot_best schedule.  Returns {"member_stats": structured array [M] like train()'s, "ensemble": {"loss_sum", "corrects"}
         (loss_mode 1: corrects is the 32.32 fixed-point F1 sum, and "f1_sum" its float value), "scores": (N, C) device tensor with
-        return_scores, "preds": int32 (M, N) device tensor with return_preds}.  Nothing a later train() reads is changed."""
+        return_scores, "preds": int32 (M, N) device tensor with return_preds}.  With report=True the same call also tallies per class
+        (mfas_population_evaluate_report) and the result gains "report": int64 numpy arrays whose first axis is the M members in list
+        order and then the ensemble — loss_mode 0: "confusion" (M+1, C, C) [slot][label][decision] and "rank_hist" (M+1, C) (the rank of
+        the label in the slot's score row); loss_mode 1: "label_counts" (M+1, C, 3) (true / predicted / actual positives per class) —
+        together with what report_metrics() derives from them.  Nothing a later train() reads is changed."""
         members, weights, combine_i = evaluate_arguments(self.K, members, weights, plane, combine, scratch_bytes,
                                                          self.hp.loss_mode, return_preds)
         M = len(members)
@@ -499,11 +503,22 @@ class Population:
         scores = torch.empty((N, self.hp.C), dtype=torch.float32, device=self.device) if return_scores else None
         preds = torch.empty((M, N), dtype=torch.int32, device=self.device) if return_preds else None
         tc = table.to_c()
-        with torch.cuda.device(self._idx):
-            _lib.check(self.lib.mfas_population_evaluate(
-                self._h, C.byref(tc), int(plane), members.ctypes.data, None if weights is None else weights.ctypes.data, M,
+        args = (self._h, C.byref(tc), int(plane), members.ctypes.data, None if weights is None else weights.ctypes.data, M,
                 combine_i, int(scratch_bytes), stats.ctypes.data, None if preds is None else C.c_void_p(preds.data_ptr()),
-                None if scores is None else C.c_void_p(scores.data_ptr()), ens.ctypes.data))
+                None if scores is None else C.c_void_p(scores.data_ptr()), ens.ctypes.data)
+        tallies = {}
+        if report:
+            nc = self.hp.C
+            shapes = {"label_counts": (M + 1, nc, 3)} if self.hp.loss_mode == 1 else {"confusion": (M + 1, nc, nc), "rank_hist": (M + 1, nc)}
+            flat = torch.empty(sum(math.prod(v) for v in shapes.values()), dtype=torch.int64, device=self.device)      # one copy back
+            at = np.cumsum([0] + [math.prod(v) for v in shapes.values()])
+            tallies = {k: flat[at[i]:at[i + 1]].view(v) for i, (k, v) in enumerate(shapes.items())}
+        with torch.cuda.device(self._idx):
+            if report:
+                _lib.check(self.lib.mfas_population_evaluate_report(
+                    *args, *(C.c_void_p(tallies[k].data_ptr()) if k in tallies else None for k in ("confusion", "rank_hist", "label_counts"))))
+            else:
+                _lib.check(self.lib.mfas_population_evaluate(*args))
         out = {"member_stats": stats, "ensemble": {"loss_sum": float(ens["dev_loss_sum"][0]), "corrects": int(ens["dev_corrects"][0])}}
         if self.hp.loss_mode == 1:
             out["ensemble"]["f1_sum"] = float(ens["dev_corrects"][0]) / F1_FIXED_POINT
@@ -511,6 +526,10 @@ class Population:
             out["scores"] = scores
         if return_preds:
             out["preds"] = preds
+        if report:
+            host = flat.cpu().numpy()
+            out["report"] = {k: host[at[i]:at[i + 1]].reshape(shapes[k]) for i, k in enumerate(shapes)}
+            out["report"].update(report_metrics(**out["report"]))
         return out
 
     def forward_train(self, k: int, table: FeatureTable, row0: int = 0, nrows: Optional[int] = None, step: int = 0):
@@ -653,6 +672,43 @@ def plan_population(hp: Hyper, confs: Sequence[np.ndarray], device, chunk_cols: 
     return {"persistent": bool(info[0]), "resident_units": int(info[1]), "resident_workgroups": int(info[2]),
             "units_per_workgroup": int(info[3]), "chunk_cols": int(info[4]), "lean_chain": bool(info[5] & 1), "wide": bool(info[5] & 2), "compute_units": int(info[6]),
             "candidates": int(info[7])}
+
+
+def _ratio(num, den):
+    """num / den in float64 with sklearn's zero_division=0 convention: a 0/0 is 0."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    return np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
+
+
+def report_metrics(confusion=None, rank_hist=None, label_counts=None, topk=(1, 5)):
+    """What a report is read for, from the integer tallies of Population.evaluate(report=True) (pure numpy, float64, no device; the
+    leading axis, if any, is the slot: members, then the ensemble).
+      confusion [.., C, C] ([label][decision]) -> "per_class_accuracy" [.., C]: the diagonal over the row sums, NaN where a class has
+        no rows.
+      rank_hist [.., C] -> "topk": {k: int64 counts [..]} of the rows whose label is among the k best classes (the running sum of the
+        histogram up to rank k - 1; k above C counts every row).
+      label_counts [.., C, 3] (true / predicted / actual positives) -> "precision", "recall", "f1" [.., C] and "f1_micro", "f1_macro",
+        "f1_weighted" [..], as sklearn's f1_score(average=...) with zero_division=0 (MM-IMDB's published figures; the reference
+        trainer lists them beside the 'samples' F1 it searches on, train_searchable/mmimdb.py:101-104)."""
+    out = {}
+    if confusion is not None:
+        cm = np.asarray(confusion, np.float64)
+        rows = cm.sum(-1)
+        out["per_class_accuracy"] = np.where(rows > 0, np.diagonal(cm, axis1=-2, axis2=-1) / np.where(rows > 0, rows, 1.0), np.nan)
+    if rank_hist is not None:
+        cum = np.cumsum(np.asarray(rank_hist, np.int64), -1)
+        for k in topk:
+            if int(k) < 1:
+                raise ValueError(f"report_metrics: top-{k} (k is at least 1)")
+        out["topk"] = {int(k): cum[..., min(int(k), cum.shape[-1]) - 1] for k in topk}
+    if label_counts is not None:
+        lc = np.asarray(label_counts, np.float64)
+        tp, npred, nact = lc[..., 0], lc[..., 1], lc[..., 2]
+        out["precision"], out["recall"], out["f1"] = _ratio(tp, npred), _ratio(tp, nact), _ratio(2.0 * tp, npred + nact)
+        out["f1_micro"] = _ratio(2.0 * tp.sum(-1), (npred + nact).sum(-1))
+        out["f1_macro"] = out["f1"].mean(-1)
+        out["f1_weighted"] = _ratio((out["f1"] * nact).sum(-1), nact.sum(-1))
+    return out
 
 
 def best_dev_f1(stats_row, status_nan: bool, n_dev: int, init_f1: float = 0.0):

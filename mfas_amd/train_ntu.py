@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import torch
 
+import numpy as np
+
 from .engine import F1_FIXED_POINT, FeatureLoader, Population, best_dev_accuracy
 from .ntu_searchable import _bump_bn_counters, _require_loader, make_order
 from .scheduler import LRCosineAnnealingScheduler
@@ -75,14 +77,35 @@ def test_ntu_track_acc(model, dataloaders, dataset_sizes, device=None, multitask
     return torch.tensor(corr / float(len(test_l.table)), dtype=torch.float64)
 
 
-def test_population_track_acc(pop, dataloaders, dataset_sizes, members=None, weights=None):
+def format_report(rep, names, n):
+    """The lines --report prints for Population.evaluate(report=True)'s "report": per slot (`names`: the members, then the ensemble)
+    top-1 / top-5 and the five worst classes (single-label), or the micro / macro / weighted F1 (multi-label)."""
+    lines = []
+    for s, name in enumerate(names):
+        if "label_counts" in rep:
+            lines.append("{} F1 micro: {:.4f} macro: {:.4f} weighted: {:.4f}".format(name, rep["f1_micro"][s], rep["f1_macro"][s],
+                                                                                 rep["f1_weighted"][s]))
+        else:
+            acc = rep["per_class_accuracy"][s]
+            worst = sorted((c for c in range(len(acc)) if acc[c] == acc[c]), key=lambda c: (acc[c], c))[:5]
+            lines.append("{} top-1: {:.4f} top-5: {:.4f} worst classes: {}".format(
+                name, rep["topk"][1][s] / n, rep["topk"][5][s] / n, ", ".join("{} ({:.3f})".format(c, acc[c]) for c in worst)))
+    return lines
+
+
+def test_population_track_acc(pop, dataloaders, dataset_sizes, members=None, weights=None, report=False):
     """The population form of test_ntu_track_acc (ntu.py:92-125): the accuracy of every member of `pop` (a Population) over
     dataloaders['test'] in eval mode, and that of their weighted ensemble (mean of the members' probabilities), from ONE
     Population.evaluate call.  Returns (float64 tensor [M] of member accuracies, 0-d float64 tensor: the ensemble's).  With
-    loss_mode 1 both are F1 'samples' averages."""
+    loss_mode 1 both are F1 'samples' averages.  report=True (--report) also prints, per member and for the ensemble, top-1 / top-5
+    and the five worst classes, or the micro / macro / weighted F1 (format_report), from the same call."""
     test_l = _require_loader(dataloaders["test"], "test", pop.device)
     n = float(len(test_l.table))
-    res = pop.evaluate(test_l.table, members=members, weights=weights)
+    res = pop.evaluate(test_l.table, members=members, weights=weights, report=report)
+    if report:
+        idx = range(pop.K) if members is None else members
+        for line in format_report(res["report"], ["Member {} (candidate {})".format(s, int(k)) for s, k in enumerate(idx)] + ["Ensemble"], n):
+            print(line)
     scale = 1.0 / F1_FIXED_POINT if pop.hp.loss_mode == 1 else 1.0
     member = torch.tensor([float(c) * scale / n for c in res["member_stats"]["dev_corrects"]], dtype=torch.float64)
     return member, torch.tensor(float(res["ensemble"]["corrects"]) * scale / n, dtype=torch.float64)
