@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 import torch.nn as nn
 
-from . import ntu_searchable as _ntu
+from . import driver as _driver
 from . import train_ntu as _tr
 from .engine import Hyper
 from .ntu_searchable import AlphaScalarMultiplication, FeatureTap, Searchable_Skeleton_Image_Net
@@ -67,8 +67,8 @@ def get_possible_layer_configurations(progression_index):
     return [[t, v, n] for t in range(5) for v in range(3) for n in range(2)]
 
 
-get_central_states = _ntu.get_central_states
-set_central_states = _ntu.set_central_states
+get_central_states = _driver.get_central_states
+set_central_states = _driver.set_central_states
 
 
 def train_sampled_models(sampled_configurations, searchable_type, dataloaders, args, device,
@@ -78,7 +78,7 @@ def train_sampled_models(sampled_configurations, searchable_type, dataloaders, a
     hp = av_hyper(args)
     if getattr(args, "multitask", False):
         hp.multitask = False     # the engine-side population path trains the central head only (see ntu driver)
-    return _ntu.train_sampled_models(sampled_configurations, searchable_type, dataloaders, args, device,
+    return _driver.train_sampled_models(sampled_configurations, searchable_type, dataloaders, args, device,
                                      return_model=return_model, premodels=premodels, preaccuracies=preaccuracies,
                                      train_only_central_params=train_only_central_params, state_dict=state_dict, _hp=hp)
 

@@ -6,8 +6,8 @@ arithmetic of the path runs inside ``libmfas_hip.so`` (mfas_amd/csrc/mfas_hip.hi
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
-from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -21,7 +21,7 @@ V_SIZES = (512, 1024, 2048, 2048)  # ntu_searchable.py:292
 TAPS = tuple(f"s{j}" for j in range(_lib.MAX_TAPS)) + tuple(f"v{j}" for j in range(_lib.MAX_TAPS))
 
 
-@dataclass
+@dataclasses.dataclass
 class Hyper:
     """The ``args`` fields the path reads (ntu_searchable.py:28-84,200-292)."""
     R: int = 16
@@ -77,6 +77,24 @@ class Hyper:
 
 def cell_in_features(conf, i, hp: Hyper) -> int:
     return hp.s_sizes[int(conf[i][0])] + hp.v_sizes[int(conf[i][1])] + (hp.R if i > 0 else 0)
+
+
+def pack_confs(confs):
+    """The configurations as the C ABI takes them: (the confs as int64 [cells, 3] arrays, cf int32 [K, 4, 3] with unused rows zero,
+    nc int32 [K] = cells per configuration)."""
+    confs = [np.asarray(c, dtype=np.int64).reshape(-1, 3) for c in confs]
+    cf = np.zeros((len(confs), 4, 3), np.int32)
+    nc = np.zeros(len(confs), np.int32)
+    for k, c in enumerate(confs):
+        if not 1 <= len(c) <= 4:
+            raise ValueError("a configuration has 1..4 fusion cells")
+        cf[k, :len(c)] = c
+        nc[k] = len(c)
+    return confs, cf, nc
+
+
+# what train() and evaluate() report per candidate and epoch (the library's mfas_epoch_stats)
+EPOCH_STATS_DTYPE = [("train_loss_sum", "f8"), ("dev_loss_sum", "f8"), ("train_corrects", "i8"), ("dev_corrects", "i8")]
 
 
 def flat_layout(conf, hp: Hyper):
@@ -254,18 +272,11 @@ class Population:
     def __init__(self, hp: Hyper, confs: Sequence[np.ndarray], device, drop_seeds=None, chunk_cols=0):
         self.lib = _lib.lib()
         self.hp = hp
-        self.confs = [np.asarray(c, dtype=np.int64).reshape(-1, 3) for c in confs]
-        self.K = len(self.confs)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("the MFAS engine runs on a HIP device only (no CPU fallback)")
-        cf = np.zeros((self.K, 4, 3), np.int32)
-        nc = np.zeros(self.K, np.int32)
-        for k, c in enumerate(self.confs):
-            if not 1 <= len(c) <= 4:
-                raise ValueError("a configuration has 1..4 fusion cells")
-            cf[k, :len(c)] = c
-            nc[k] = len(c)
+        self.confs, cf, nc = pack_confs(confs)
+        self.K = len(self.confs)
         ds = None if drop_seeds is None else np.asarray(drop_seeds, np.uint32)
         self._used_taps = {}        # tap name -> (declared width, first configuration / cell that selects it)
         for k, c in enumerate(self.confs):
@@ -389,8 +400,7 @@ class Population:
         for t in (train, dev):
             if t is not None:
                 self._check_table(t)
-        stats = np.zeros((self.K, epochs), dtype=[("train_loss_sum", "f8"), ("dev_loss_sum", "f8"),
-                                                  ("train_corrects", "i8"), ("dev_corrects", "i8")])
+        stats = np.zeros((self.K, epochs), dtype=EPOCH_STATS_DTYPE)
         status = np.zeros(self.K, np.int32)
         tt = train.to_c()
         td = dev.to_c() if dev is not None else None
@@ -497,7 +507,7 @@ class Population:
         if self.hp.loss_mode == 0:      # the kernels index by the label
             table.check_labels(self.hp.C)
         self._check_table(table)
-        stats = np.zeros(M, dtype=[("train_loss_sum", "f8"), ("dev_loss_sum", "f8"), ("train_corrects", "i8"), ("dev_corrects", "i8")])
+        stats = np.zeros(M, dtype=EPOCH_STATS_DTYPE)
         ens = np.zeros(1, dtype=stats.dtype)
         N = len(table)
         scores = torch.empty((N, self.hp.C), dtype=torch.float32, device=self.device) if return_scores else None
@@ -593,22 +603,24 @@ class Population:
         return int(n.value), float(ms.value), float(by.value)
 
 
+def _hyper_dict(hp: Hyper):
+    """The Hyper as a checkpoint holds it (sequences as lists: what torch.load(weights_only=True) gives back)."""
+    return {key: (list(v) if isinstance(v, (tuple, list)) else v) for key, v in dataclasses.asdict(hp).items()}
+
+
 def save_checkpoint(path: str, pop: Population):
     """torch.save of every candidate's export_candidate() state (host tensors) with the configurations and the Hyper."""
-    import dataclasses
     cands = []
     for k in range(pop.K):
         st = pop.export_candidate(k)
         cands.append({key: (v.cpu() if torch.is_tensor(v) else v) for key, v in st.items()})
-    hyper = {key: (list(v) if isinstance(v, (tuple, list)) else v) for key, v in dataclasses.asdict(pop.hp).items()}
-    torch.save({"format": 1, "hyper": hyper, "confs": [c.tolist() for c in pop.confs], "candidates": cands}, path)
+    torch.save({"format": 1, "hyper": _hyper_dict(pop.hp), "confs": [c.tolist() for c in pop.confs], "candidates": cands}, path)
 
 
 def load_checkpoint(path: str, pop: Population):
     """Load a save_checkpoint file into `pop`; a file written for other configurations or another Hyper is refused."""
-    import dataclasses
     ck = torch.load(path, map_location="cpu", weights_only=True)
-    mine = {key: (list(v) if isinstance(v, (tuple, list)) else v) for key, v in dataclasses.asdict(pop.hp).items()}
+    mine = _hyper_dict(pop.hp)
     diff = sorted(key for key in set(mine) | set(ck["hyper"]) if mine.get(key) != ck["hyper"].get(key))
     if diff:
         raise ValueError("checkpoint was written for another Hyper: " +
@@ -656,14 +668,7 @@ def plan_population(hp: Hyper, confs: Sequence[np.ndarray], device, chunk_cols: 
     """mfas_population_plan: the schedule mfas_population_create would lay these configurations out for — a pure query (nothing
     is allocated or launched).  Keys as Population.schedule() where they apply."""
     lib = _lib.lib()
-    confs = [np.asarray(c, dtype=np.int64).reshape(-1, 3) for c in confs]
-    cf = np.zeros((len(confs), 4, 3), np.int32)
-    nc = np.zeros(len(confs), np.int32)
-    for k, c in enumerate(confs):
-        if not 1 <= len(c) <= 4:
-            raise ValueError("a configuration has 1..4 fusion cells")
-        cf[k, :len(c)] = c
-        nc[k] = len(c)
+    confs, cf, nc = pack_confs(confs)
     dev = torch.device(device)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     info = np.zeros(8, np.int32)

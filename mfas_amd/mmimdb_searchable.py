@@ -14,10 +14,10 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ntu_searchable as _ntu
-from .engine import FeatureLoader, Hyper, Population, best_dev_f1
-from .ntu_searchable import Searchable_Skeleton_Image_Net, _bump_bn_counters, _require_loader, make_order
-from .scheduler import LRCosineAnnealingScheduler
+from . import driver as _driver
+from .driver import _require_loader, etas_for, train_one
+from .engine import Hyper, best_dev_f1
+from .ntu_searchable import Searchable_Skeleton_Image_Net
 
 MM_TEXT_SIZES = (64, 128, 64, 128)      # two real taps; slots 2/3 alias them so the 4-slot table layout is reused
 MM_IMAGE_SIZES = (512, 512, 512, 512)
@@ -73,31 +73,20 @@ def train_mmimdb_track_f1(model, criterion, optimizer, scheduler, dataloaders, d
     device = torch.device(device) if device is not None else train_l.table.device
     hp = mm_hyper(model.args, th_fscore)
     hp.B = train_l.batch_size
+    # Kept apart from train_ntu_track_acc on purpose: only weight_decay is read from the optimizer (train_ntu._adam_hyper reads betas
+    # and eps too), and tap_bits stays unset (setting it can change the plan, and with it the summation order).
     if optimizer is not None and getattr(optimizer, "param_groups", None):
         g = optimizer.param_groups[0]
         hp.wd = float(g.get("weight_decay", hp.wd))
     N_tr, N_dev = len(train_l.table), len(dev_l.table)
-    nb = -(-N_tr // hp.B)
-    if isinstance(scheduler, LRCosineAnnealingScheduler):
-        etas = scheduler.eta_table(num_epochs * nb)
-    else:
-        for _ in range(num_epochs):
-            scheduler.step()
-        etas = [optimizer.param_groups[0]["lr"]] * (num_epochs * nb)
+    etas = etas_for(scheduler, optimizer, num_epochs, -(-N_tr // hp.B))
     seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-    pop = Population(hp, [model.conf], device, drop_seeds=[seed & 0xFFFFFFFF])
-    pop.set_pos_weight(getattr(criterion, "w", np.ones(hp.C, np.float32)))
-    pop.set_params(0, model.flat_params())
-    order = make_order(N_tr, num_epochs, train_l.shuffle, seed + 1, device)
-    pop.set_best_threshold(float(init_f1))      # best_f1 = init_f1 (mmimdb.py:18): the kept weights follow the same threshold
-    stats, status = pop.train(train_l.table, dev_l.table, num_epochs, etas, order=order, snapshot_best=True)
+    # best_f1 = init_f1 (mmimdb.py:18): the kept weights follow the same threshold
+    stats, status = train_one(model, hp, train_l, dev_l, num_epochs, etas, device, drop_seed=seed, order_seed=seed + 1,
+                              pos_weight=getattr(criterion, "w", np.ones(hp.C, np.float32)), best_threshold=init_f1)
     if verbose:
         for e in range(num_epochs):
             print("epoch #{} dev F1: {:.4f} ".format(e, stats["dev_corrects"][0, e] / float(1 << 32) / N_dev))
-    model.load_flat(pop.get_params(0))
-    _bump_bn_counters(model, num_epochs * nb)
-    pop.close()
-    model.train(False)
     return best_dev_f1(stats[0], bool(status[0]), N_dev, init_f1)
 
 
@@ -108,7 +97,7 @@ def train_sampled_models(sampled_configurations, searchable_type, dataloaders, a
     the best dev F1-samples per configuration.  args.pos_weight (list of C floats) weights the positives."""
     pw = getattr(args, "pos_weight", None)
     pw = np.ones(int(args.num_outputs), np.float32) if pw is None else np.asarray(pw, np.float32)
-    return _ntu.train_sampled_models(sampled_configurations, searchable_type, dataloaders, args, device,
+    return _driver.train_sampled_models(sampled_configurations, searchable_type, dataloaders, args, device,
                                      return_model=return_model, premodels=premodels, preaccuracies=preaccuracies,
                                      train_only_central_params=train_only_central_params, state_dict=state_dict,
                                      _hp=mm_hyper(args, getattr(args, "th_fscore", 0.3)), _pos_weight=pw)

@@ -193,7 +193,7 @@ def predicted_step_us(share_costs: Sequence[int], R: int) -> float:
         for cap, us in RESIDENT_STEP_US:
             if n <= cap:
                 return us
-        if n <= 2 * RESIDENT_STEP_US[-1][0]:      # two resident rounds, one after the other (ntu_searchable._plan_rounds)
+        if n <= 2 * RESIDENT_STEP_US[-1][0]:      # two resident rounds, one after the other (driver._plan_rounds)
             return 2.0 * RESIDENT_STEP_US[-1][1]
         return max(38.0, 12.0 + bytes_us)         # launch-per-phase, lean chain
     return max(52.0 * min(1.0, R / 128.0) + 15.0, 35.0 + bytes_us)     # general chain: its latency, or the stream

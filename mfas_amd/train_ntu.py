@@ -8,14 +8,11 @@ from __future__ import annotations
 
 import torch
 
-import numpy as np
-
-from .engine import F1_FIXED_POINT, FeatureLoader, Population, best_dev_accuracy
-from .ntu_searchable import _bump_bn_counters, _require_loader, make_order
-from .scheduler import LRCosineAnnealingScheduler
+from .driver import _require_loader, etas_for, print_epoch_stats, tap_bits_of, train_one
+from .engine import F1_FIXED_POINT, Population, best_dev_accuracy
 
 
-def _adam_hyper(hp, optimizer):
+def _adam_hyper(hp, optimizer):      # (train_mmimdb_track_f1 reads weight_decay ALONE from its optimizer: kept apart on purpose)
     if optimizer is not None and getattr(optimizer, "param_groups", None):
         g = optimizer.param_groups[0]
         hp.wd = float(g.get("weight_decay", hp.wd))
@@ -36,31 +33,13 @@ def train_ntu_track_acc(model, criteria, optimizer, scheduler, dataloaders, data
     model = model.module if isinstance(model, torch.nn.DataParallel) else model
     hp = _adam_hyper(model.hyper(multitask), optimizer)
     hp.B = train_l.batch_size
-    hp.tap_bits = 8 * train_l.table.elem_size() if train_l.table.dtype == dev_l.table.dtype else 0
+    hp.tap_bits = tap_bits_of(train_l.table, dev_l.table)
     N_tr, N_dev = len(train_l.table), len(dev_l.table)
-    nb = -(-N_tr // hp.B)
-    if isinstance(scheduler, LRCosineAnnealingScheduler):
-        etas = scheduler.eta_table(num_epochs * nb)
-    else:   # ntu.py:24-26: other schedulers are stepped once per epoch and never pushed to the optimizer
-        for _ in range(num_epochs):
-            scheduler.step()
-        lr = optimizer.param_groups[0]["lr"]
-        etas = [lr] * (num_epochs * nb)
+    etas = etas_for(scheduler, optimizer, num_epochs, -(-N_tr // hp.B))
     seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-    pop = Population(hp, [model.conf], device, drop_seeds=[seed & 0xFFFFFFFF])
-    pop.set_params(0, model.flat_params())
-    order = make_order(N_tr, num_epochs, train_l.shuffle, seed + 1, device)
-    stats, _ = pop.train(train_l.table, dev_l.table, num_epochs, etas, order=order, snapshot_best=True)
+    stats, _ = train_one(model, hp, train_l, dev_l, num_epochs, etas, device, drop_seed=seed, order_seed=seed + 1)
     if verbose:
-        for e in range(num_epochs):
-            print("train Loss: {:.4f} Acc: {:.4f}".format(stats["train_loss_sum"][0, e] / N_tr,
-                                                          stats["train_corrects"][0, e] / N_tr))
-            print("dev Loss: {:.4f} Acc: {:.4f}".format(stats["dev_loss_sum"][0, e] / N_dev,
-                                                        stats["dev_corrects"][0, e] / N_dev))
-    model.load_flat(pop.get_params(0))
-    _bump_bn_counters(model, num_epochs * nb)
-    pop.close()
-    model.train(False)
+        print_epoch_stats(stats[0], N_tr, N_dev)
     return torch.tensor(best_dev_accuracy(stats[0], N_dev), dtype=torch.float64)
 
 
@@ -70,6 +49,7 @@ def test_ntu_track_acc(model, dataloaders, dataset_sizes, device=None, multitask
     device = torch.device(device) if device is not None else test_l.table.device
     model = model.module if isinstance(model, torch.nn.DataParallel) else model
     model.train(False)
+    # (tap_bits stays unset here: setting it can change the plan, and with it the summation order)
     pop = Population(model.hyper(multitask), [model.conf], device)
     pop.set_params(0, model.flat_params())
     _, corr = pop.forward(0, test_l.table, count=True)

@@ -4,7 +4,7 @@ import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mfas_amd as M
-from mfas_amd import ntu_searchable as NS, engine as EN
+from mfas_amd import ntu_searchable as NS, driver as DR, engine as EN
 from types import SimpleNamespace
 K = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 dev = torch.device("cuda:0")
@@ -25,7 +25,7 @@ def wrap(mod, name):
         return r
     setattr(mod, name, g)
 for n in ("_init_population_device_streams", "make_order_per_candidate", "_init_population_from_torch"):
-    wrap(NS, n)
+    wrap(DR, n)
 for n in ("train", "close", "__init__"):
     f = getattr(EN.Population, n)
     def mk(f, n):
