@@ -47,7 +47,7 @@ def is_tap(k):
 
 
 def _dequant(a, dtype):
-    from tests.test_gpu_ref64 import dequant
+    from tests.ref64_cases import dequant
     return dequant(a, dtype)
 
 

@@ -7,17 +7,11 @@ import pytest
 
 from oracle import np_oracle as O
 from tests.helpers import engine_hyper, etas_for, golden
-
-SS, VS = (3, 6, 12, 24, 48), (3, 6, 12)
+from tests.avmnist_cases import SS, VS, tables
 
 
 def hyper():
     return O.Hyper(R=16, C=10, B=16, bn=False, drpt=0.0, epochs=3, s_sizes=SS, v_sizes=VS, allow_plain_cell=True)
-
-
-def tables():
-    return (O.synth_table(192, 71, snr=1.0, C=10, s_sizes=SS, v_sizes=VS),
-            O.synth_table(96, 72, snr=1.0, C=10, s_sizes=SS, v_sizes=VS))
 
 
 def test_oracle_vs_reference_avmnist():

@@ -6,7 +6,7 @@ the three statements that replace "create sets the LDS limit of everything":
 * every key of any plan_keys has a row in the kernel tables (the row lists the library compiles into them), and no plan_keys names
   a key twice;
 * every table row is in some plan_keys, except the k_eval builds no accepted geometry reaches
-  (test_gpu_report_ref64.UNREACHABLE_BUILDS, each with its reason): a dead build cannot come back unnoticed.
+  (report_cases.UNREACHABLE_BUILDS, each with its reason): a dead build cannot come back unnoticed.
 
 The domain: test_step_builds_cpu.plan_states() x {cached, nontemporal} and the resident plans (the lean chain at MB <= 2, one or two
 units per workgroup, narrow or wide units), each with the dev-pass facts of every geometry R <= 512, C <= 256 its chain admits
@@ -20,9 +20,9 @@ import pytest
 
 from oracle import np_oracle as O
 from tests import builds_header as BH
-from tests import test_gpu_ref64 as G
-from tests import test_gpu_report_ref64 as RP
-from tests import test_step_builds_cpu as SB
+from tests import ref64_cases as G
+from tests import report_cases as RP
+from tests import step_build_cases as SB
 
 
 def eval_geometries():

@@ -41,11 +41,11 @@ import pytest
 
 from oracle import np_oracle as O
 from tests import ref64 as R64
-from tests import test_axes_cpu as AX
-from tests import test_gpu_ref64 as G
-from tests import test_gpu_resident_ref64 as GR
-from tests import test_gpu_train_ref64 as GT
-from tests.test_gpu_ref64 import dev  # noqa: F401
+from tests import axes_cases as AX
+from tests import gpu_support as G
+from tests import resident_cases as GR
+from tests import train_gpu as GT
+from tests.gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -141,7 +141,7 @@ def check_population_entry_points(dev, pop, inp, tag, rec):
 
 @pytest.mark.parametrize("spec", AX.POPS, ids=AX.POP_IDS)
 def test_population_steps_vs_ref64(dev, spec):
-    """One population of test_axes_cpu.POPS (a train schedule or the wide path, asserted by name; K >= 3 candidates of different
+    """One population of axes_cases.POPS (a train schedule or the wide path, asserted by name; K >= 3 candidates of different
     depth and nonlinearity): steps 1..3 of every candidate against ref64.  Plain-cell populations also run the entry points and
     the dev pass; a set whose learning rates are exactly 0 leaves w bit-identical while m and v move."""
     torch = G._torch()

@@ -12,16 +12,11 @@ import pytest
 torch = pytest.importorskip("torch")
 from oracle import np_oracle as O
 from tests.helpers import CONFS, engine_hyper
+from tests.gpu_dev import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TINY = ["--epochs", "1", "--n-train", "320", "--n-dev", "160", "--no-cpu-baseline"]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "needs a HIP device"
-    return torch.device("cuda:0")
 
 
 def run_bench(extra, timeout=900):

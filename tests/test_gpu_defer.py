@@ -16,11 +16,11 @@ import numpy as np
 import pytest
 
 from oracle import np_oracle as O
-from tests import test_gpu_ref64 as G
-from tests import test_gpu_step_builds_ref64 as GB
-from tests import test_gpu_train_ref64 as GT
-from tests import test_step_builds_cpu as SB
-from tests.test_gpu_ref64 import dev  # noqa: F401
+from tests import ref64_cases as G
+from tests import step_build_gpu as GB
+from tests import train_cases as GT
+from tests import step_build_cases as SB
+from tests.gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

@@ -30,6 +30,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tests.gpu_dev import dev  # noqa: E402,F401
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "driver_digests.json")
@@ -74,6 +76,7 @@ def np_table(n, seed, s_sizes, v_sizes, nclass, multilabel=False):
     return t
 
 
+# (tests/mirror_gpu.py's loaders takes tables; this one draws its own of the given widths, with multi-hot targets on request)
 def loaders(dev, s_sizes, v_sizes, nclass, multilabel=False):
     import torch
     import mfas_amd as M
@@ -263,13 +266,6 @@ def run_case(name, dev):
         M.Population.train = real_train
     assert seen, name
     return {**got, "population.train": sha(*seen)}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -24,58 +24,22 @@ import pytest
 
 from oracle import np_oracle as O
 from tests import ref64 as R64
-from tests import test_evaluate_cpu as EC
-from tests import test_gpu_ref64 as G
-from tests.test_gpu_ref64 import dev  # noqa: F401
-from tests.test_gpu_report_ref64 import make_population, plane_bytes
+from tests import evaluate_cases as EC
+from tests import gpu_support as G
+from tests.gpu_support import dev  # noqa: F401
+from tests.report_gpu import make_population, plane_bytes
+from tests.evaluate_gpu import COMBINE, close_worlds, evaluate, outputs, world
 
 pytestmark = pytest.mark.gpu
 
 F32, F64 = np.float32, np.float64
 U = R64.U
-COMBINE = ("prob", "score")
-
-
-# ------------------------------------------------------------------------------------------------ plumbing
-_WORLDS = {}
-
-
-def world(cid, dev):
-    """One population per case with its parameters loaded, the table on the device, and the engine's OWN float32 logits and counts
-    of every candidate from forward() — computed once, shared by the tests, never changed."""
-    if cid not in _WORLDS:
-        from tests.helpers import engine_hyper
-        case = EC.EVAL_CASES[EC.EVAL_IDS.index(cid)]
-        inp = EC.eval_inputs(case)
-        hp = inp["hp"]
-        pop = make_population(engine_hyper(hp), inp["confs"], dev, inp["seeds"], pos_weight=G.pos_weight(hp) if hp.loss_mode else None)
-        for k, p in enumerate(inp["p0s"]):
-            pop.set_state_dict(k, p)
-        tab = G.gpu_table(inp["tab"], inp["dtype"], dev)
-        fwd = [pop.forward(k, tab, count=True) for k in range(pop.K)]
-        inp.update(pop=pop, gtab=tab, Z=np.stack([f[0].cpu().numpy() for f in fwd]), counts=[f[1] for f in fwd], case=case)
-        _WORLDS[cid] = inp
-    return _WORLDS[cid]
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _close_worlds():
     yield
-    for w in _WORLDS.values():
-        w["pop"].close()
-    _WORLDS.clear()
-
-
-def evaluate(w, members, weights, combine, **kw):
-    lm0 = w["hp"].loss_mode == 0
-    return w["pop"].evaluate(w["gtab"], members=members, weights=weights, combine=COMBINE[combine], return_scores=True,
-                             return_preds=lm0, **kw)
-
-
-def outputs(res):
-    """Everything k_vote wrote, as bytes / integers (for bit-identity)."""
-    return (res["scores"].cpu().numpy().tobytes(), res["preds"].cpu().numpy().tobytes() if "preds" in res else b"",
-            np.float64(res["ensemble"]["loss_sum"]).tobytes(), res["ensemble"]["corrects"], res["member_stats"]["dev_corrects"].tolist())
+    close_worlds()
 
 
 def statement(w, members, weights, combine, Z=None, dz=None):

@@ -19,12 +19,12 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import test_evaluate_cpu as EC
-from tests import test_evaluate_report_cpu as RC
-from tests import test_gpu_evaluate_ref64 as EV
-from tests import test_gpu_ref64 as G
-from tests.test_gpu_ref64 import dev  # noqa: F401
-from tests.test_gpu_report_ref64 import make_population
+from tests import evaluate_cases as EC
+from tests import evaluate_report_cases as RC
+from tests import evaluate_gpu as EV
+from tests import gpu_support as G
+from tests.gpu_support import dev  # noqa: F401
+from tests.report_gpu import make_population
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +35,7 @@ KEYS = ("confusion", "rank_hist", "label_counts")
 
 # ------------------------------------------------------------------------------------------------ plumbing
 def _build(inp, case, dev):
-    """What test_gpu_evaluate_ref64.world builds, for inputs of this file's own."""
+    """What evaluate_gpu.world builds, for inputs of this file's own."""
     from tests.helpers import engine_hyper
     hp = inp["hp"]
     pop = make_population(engine_hyper(hp), inp["confs"], dev, inp["seeds"], pos_weight=G.pos_weight(hp) if hp.loss_mode else None)
@@ -48,19 +48,17 @@ def _build(inp, case, dev):
 
 
 def world(cid, dev):
-    """test_gpu_evaluate_ref64.world; a case of EXTRA_CASES enters its cache built the same way."""
-    if cid in RC.EXTRA_CASES and cid not in EV._WORLDS:
+    """evaluate_gpu.world; a case of EXTRA_CASES enters its cache built the same way."""
+    if cid in RC.EXTRA_CASES:
         case = RC.EXTRA_CASES[cid][0]
-        EV._WORLDS[cid] = _build(RC.report_inputs(case), case, dev)
+        EV.add_world(cid, lambda: _build(RC.report_inputs(case), case, dev))
     return EV.world(cid, dev)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _close_worlds():
     yield
-    for w in EV._WORLDS.values():
-        w["pop"].close()
-    EV._WORLDS.clear()
+    EV.close_worlds()
 
 
 def arrays(res):

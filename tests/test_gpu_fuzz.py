@@ -10,8 +10,8 @@ torch = pytest.importorskip("torch")
 from oracle import np_oracle as O
 from tests import ref64 as R64
 from tests.helpers import engine_hyper, etas_for, oracle_steps, rel_err
-from tests.test_gpu_ref64 import TAU_LOGITS
-from tests.test_gpu_parity import check_state, mk_pop, table
+from tests.ref64_cases import TAU_LOGITS
+from tests.parity_gpu import check_state, mk_pop, table
 
 pytestmark = pytest.mark.gpu
 

@@ -1,7 +1,7 @@
 """The kernels against the float64 reference on degenerate and extreme input VALUES (tests/input_edges.py), where every other
 ref64 file varies the shapes and draws the values from one distribution.
 
-Each entry of test_inputs_cpu.INPUT_CASES (base case, transform, table dtype) runs the four blocks of
+Each entry of input_cases.INPUT_CASES (base case, transform, table dtype) runs the four blocks of
 test_gpu_ref64.py::test_entry_points_vs_ref64 on the transformed inputs — the eval forward over the ragged row ranges in every
 dev-pass build, forward_train + running statistics, backward of arbitrary dlogits, one epoch of train() with a dev table — and
 steps 1, 2 and 3 of train() as test_gpu_train_ref64.py checks them.  Same rule, same taus: |got - ref64| <= tau 2^-24 M
@@ -12,7 +12,7 @@ elementwise (logits 6, gradients 20, running statistics 4; steps: m 20, v 1, w 2
 * 'dup' / 'dead' / 'deadrelu' with BatchNorm: a named column has batch variance 0 in ref64's own forward (so the case cannot
   silently stop being degenerate; 'deadrelu': a column of the FIRST cell, a ReLU, exactly 0 on every row); its running variance moves
   by exactly the momentum step towards 0, which the elementwise check holds;
-* 'bigmean' and the wide 'dup' (test_inputs_cpu.FLAGGED) are judged with ref64's batch_sum_term — the rounding of the two batch sums
+* 'bigmean' and the wide 'dup' (input_cases.FLAGGED) are judged with ref64's batch_sum_term — the rounding of the two batch sums
   themselves added to M_mu and M_var (tests/ref64.py::forward) — in forward_train, backward and the train steps; every other entry,
   'deadrelu' included, without it.  The taus are the same;
 * POP_CASES: one candidate of a population transformed ('dead', 'bighead', 'deadrelu'), on the resident schedule, on chain_split, on
@@ -57,11 +57,11 @@ import pytest
 from oracle import np_oracle as O
 from tests import input_edges as IE
 from tests import ref64 as R64
-from tests import test_gpu_ref64 as G
-from tests import test_gpu_train_ref64 as GT
-from tests import test_gpu_wide_ref64 as GW
-from tests import test_inputs_cpu as TI
-from tests.test_gpu_ref64 import dev  # noqa: F401
+from tests import gpu_support as G
+from tests import train_gpu as GT
+from tests import wide_gpu as GW
+from tests import input_cases as TI
+from tests.gpu_support import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

@@ -8,29 +8,10 @@ import pytest
 torch = pytest.importorskip("torch")
 from oracle import np_oracle as O
 from tests.helpers import CONFS, golden
+from tests.mirror_gpu import loaders, mkargs
+from tests.gpu_dev import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "needs a HIP device"
-    return torch.device("cuda:0")
-
-
-def mkargs(**kw):
-    a = dict(vid_len=(8, 32), num_outputs=60, drpt=0.5, inner_representation_size=16, batchnorm=False,
-             alphas=False, multitask=False, weightsharing=False, batchsize=16, eta_max=1e-3, eta_min=1e-6,
-             Ti=1, Tm=2, use_dataparallel=False, verbose=False, epochs=3)
-    a.update(kw)
-    return SimpleNamespace(**a)
-
-
-def loaders(ttr, tdv, dev, B, shuffle=True, dtype=torch.float32):
-    import mfas_amd as M
-    return {"train": M.FeatureLoader(M.FeatureTable.from_numpy(ttr, dev, dtype), B, shuffle=shuffle),
-            "dev": M.FeatureLoader(M.FeatureTable.from_numpy(tdv, dev, dtype), B, shuffle=False),
-            "test": M.FeatureLoader(M.FeatureTable.from_numpy(tdv, dev, dtype), B, shuffle=False)}
 
 
 def test_train_sampled_models_signature_and_determinism(dev):
@@ -802,7 +783,7 @@ def test_bf16x3_eval_products_match_f32_products(dev, R, bn, alphas, K, mixed, w
     # both builds against the float64 reference on the trained parameters, elementwise (tests/ref64.py): a B3 build that lost the
     # low weight bits would still pass the max-scaled bound above
     from tests import ref64 as R64
-    from tests.test_gpu_ref64 import TAU_LOGITS
+    from tests.ref64_cases import TAU_LOGITS
     dv = O.synth_table(Nd, 4, snr=0.6, **okw)
     feats = {key: O.bf16_round(v)[3:Nd - 2] for key, v in dv.items() if key[0] in "sv"}
     for k in range(K):

@@ -7,14 +7,9 @@ import pytest
 torch = pytest.importorskip("torch")
 from oracle import np_oracle as O
 from tests.helpers import engine_hyper, etas_for, golden
+from tests.gpu_dev import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def mm_table(t, dev, dtype=torch.float32):
@@ -53,7 +48,7 @@ def test_multilabel_engine_vs_reference_golden(dev, tag, R):
 def test_multilabel_steps_and_fp16(dev):
     """A few train steps with dropout (shared mask stream) on fp16-stored taps: parameters track the oracle."""
     from mfas_amd import Population
-    from tests.test_gpu_parity import check_state
+    from tests.parity_gpu import check_state
     from tests.helpers import oracle_steps
     conf = np.array([[1, 3, 0], [0, 1, 1], [1, 0, 0]])
     w = O.mm_pos_weight(23)
@@ -123,7 +118,7 @@ def test_searchers_for_the_other_datasets(dev):
     confs, f1s, _ = data.get_k_best(3)
     assert len(confs) == 3 and all(0.0 < f <= 1.0 for f in f1s) and max(len(c) for c in confs) <= 2
     # AV-MNIST, random-search driver
-    from tests.test_avmnist import tables as av_tables
+    from tests.avmnist_cases import tables as av_tables
     ttr, tdv = av_tables()
     args = SimpleNamespace(num_outputs=10, channels=3, randsearch=True, **common)
     tabs = {"train": M.FeatureTable.from_numpy(ttr, dev), "dev": M.FeatureTable.from_numpy(tdv, dev)}

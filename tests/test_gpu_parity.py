@@ -15,24 +15,10 @@ import pytest
 torch = pytest.importorskip("torch")
 from oracle import np_oracle as O
 from tests.helpers import CONFS, engine_hyper, etas_for, frac_bad, golden, oracle_steps, rel_err  # noqa: F401
+from tests.parity_gpu import check_state, mk_pop, table
+from tests.gpu_dev import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "needs a HIP device"
-    return torch.device("cuda:0")
-
-
-def mk_pop(ohp, confs, dev, **kw):
-    from mfas_amd import Population
-    return Population(engine_hyper(ohp), [np.array(c) for c in confs], dev, **kw)
-
-
-def table(t, dev, dtype=torch.float32):
-    from mfas_amd import FeatureTable
-    return FeatureTable.from_numpy(t, dev, dtype)
 
 
 # ---------------------------------------------------------------------------------------- provenance
@@ -96,63 +82,6 @@ def test_eval_forward_vs_reference_golden(dev):
         pop.close()
         n += 1
     assert n >= 15
-
-
-# ---------------------------------------------------------------------------------------- k train steps vs oracle AND reference golden
-def _row_block_fracs(a, v, rtol, atol):
-    """Fraction of out-of-tolerance elements per 16-row block of a weight matrix (the engine's tile rows)."""
-    bad = np.abs(a - v) > atol + rtol * np.abs(v)
-    nrb = -(-a.shape[0] // 16)
-    return np.array([bad[16 * rb:16 * rb + 16].mean() for rb in range(nrb)])
-
-
-def check_state(pop, k, params, st, steps, lr=1e-3, tag=""):
-    """Parameters / Adam moments after `steps` train steps vs the oracle.  Adam's first steps are sign-like (dw = +-lr for every
-    element whatever the size of its gradient), so elements whose gradient is round-off sized may legitimately land up to
-    lr * steps apart; everything else has to agree to 1e-4.  Three layers of bounds:
-      * bulk:       >= 99 % of the elements (94 % for vectors under 1000 elements) within rtol 1e-4;
-      * tail:       >= 99.9 % within rtol 1e-2 (+ the same atol) — the sign-flip elements are few AND the rest is tight;
-      * max:        every element within 2 lr * steps (a sign flip of a round-off-sized gradient);
-      * structure:  no 16-row tile block of a weight matrix may hold more than 4x its share of the out-of-tolerance elements
-                    (an indexing error confined to one tile row cannot hide inside the global allowance).
-    Observed over the 2,300 tensors the GPU suite checks (MFAS_CHECK_STATS=<file> logs them): bulk <= 0.29 %, tail <= 0.03 %,
-    worst row block <= 1.8 % for tensors of >= 1000 elements; the limits sit ~3x above that."""
-    import os
-    got = pop.get_state_dict(k, 0)
-    gm = pop.get_state_dict(k, 1)
-    gv = pop.get_state_dict(k, 2)
-    log = os.environ.get("MFAS_CHECK_STATS")
-    for key, v in params.items():
-        if key.startswith("alphas") and key not in st.m:
-            continue
-        a = got[key].numpy()
-        lim = 0.01 if a.size >= 1000 else 0.06          # small vectors: a handful of round-off-level elements
-        # BN running statistics are an EMA of batch moments: they inherit the weights' allowed 1e-4 deviations of every step
-        rtol = 1e-3 if key.endswith(("running_mean", "running_var")) else 1e-4
-        atol = 2e-6 * steps
-        fb = frac_bad(a, v, rtol, atol)
-        ft = frac_bad(a, v, 1e-2, atol)
-        rbmax = 0.0
-        if a.ndim == 2 and a.shape[0] >= 32 and a.size >= 4096:
-            rbf = _row_block_fracs(a, v, rtol, atol)
-            rbmax = float(rbf.max())
-            assert rbmax <= max(0.03, 4.0 * fb + 0.01), (tag, key, "row-block", rbf.round(3).tolist())
-        if log:
-            with open(log, "a") as f:
-                f.write(f"{tag} {key} n={a.size} bulk={fb:.5f} tail={ft:.5f} rbmax={rbmax:.5f} max={np.abs(a - v).max():.3g}\n")
-        assert fb <= lim, (tag, key, fb)
-        assert ft <= (0.001 if a.size >= 1000 else 0.03), (tag, key, "tail", ft)
-        # (|dw| = lr at step 1 whatever |g| is: a round-off-sized gradient with the opposite SIGN lands 2 lr away; the tail bound
-        #  above keeps such elements under 0.1 %)
-        assert np.abs(a - v).max() <= 2.0 * lr * steps, (tag, key)
-    for key in st.m:
-        # small vectors: a ReLU/dropout kink flipped by round-off moves one sample's share of a column sum (1/B), so a
-        # handful of isolated elements may sit a few % off
-        lim = 0.03 if st.m[key].size >= 1000 else max(0.06, 3.0 / st.m[key].size)
-        sc = float(np.abs(st.m[key]).max()) + 1e-30
-        assert frac_bad(gm[key].numpy(), st.m[key], 2e-3, 2e-3 * sc) <= lim, (tag, "m", key)
-        sc = float(np.abs(st.v[key]).max()) + 1e-30
-        assert frac_bad(gv[key].numpy(), st.v[key], 4e-3, 2e-3 * sc) <= lim, (tag, "v", key)
 
 
 @pytest.mark.parametrize("cname,R", [("c4", 16), ("c4", 128), ("l2", 16)])

@@ -23,7 +23,8 @@ import numpy as np
 import pytest
 
 from tests import input_edges as IE
-from tests.test_gpu_ref64 import dev  # noqa: F401
+from tests.gpu_support import dev  # noqa: F401
+from tests.pool_cases import rne16
 
 pytestmark = pytest.mark.gpu
 
@@ -32,28 +33,6 @@ INNERS = (1, 3, 4, 7, 8, 9, 63, 64, 65, 255, 257, 1001, 8192)
 ROWS = {1: (1, 1), 3: (1, 3), 4: (2, 2), 5: (5, 1), 130: (2, 65)}
 DTYPES = ("float32", "bfloat16", "float16")
 WORST = {}
-
-
-def rne_bf16(x):
-    """float64 -> the nearest bfloat16 (ties to even), as float64: rounded once, not through float32."""
-    x = np.asarray(x, np.float64)
-    a = np.abs(x)
-    f = a.astype(np.float32)
-    f = np.where(f.astype(np.float64) > a, np.nextafter(f, np.float32(0)), f).astype(np.float32)      # toward zero
-    bits = f.view(np.uint32) & np.uint32(0xFFFF0000)
-    d = bits.view(np.float32).astype(np.float64)
-    u = (bits + np.uint32(0x10000)).view(np.float32).astype(np.float64)
-    mid = 0.5 * (d + u)
-    even_down = ((bits >> np.uint32(16)) & np.uint32(1)) == 0
-    r = np.where(a > mid, u, np.where(a < mid, d, np.where(even_down, d, u)))
-    return np.copysign(r, x)
-
-
-def rne16(x, out_dtype):
-    if out_dtype == "bfloat16":
-        return rne_bf16(x)
-    with np.errstate(over="ignore"):
-        return np.asarray(x, np.float64).astype(np.float16).astype(np.float64)
 
 
 def check_pool(x, out_dtype, tag):

@@ -18,6 +18,7 @@ import mfas_amd as M
 from mfas_amd import ntu_searchable as NS
 from mfas_amd.engine import load_checkpoint, save_checkpoint
 from oracle import np_oracle as O
+from tests.gpu_dev import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -38,12 +39,6 @@ CASES = {
     "chain_split": (128, 16, 2, {}, 0, True, 0, lambda s: s["groups"] == -1 and s["chain_cus"] == 4),
     "wide": (80, 33, 2, {}, 0, True, 0, lambda s: s["wide"] == 1 and s["persistent"] == 0),
 }
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "needs a HIP device"
-    return torch.device("cuda:0")
 
 
 def make_table(n, seed, dev, loss_mode):

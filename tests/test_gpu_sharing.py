@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 HIST_RE = r"(train|dev) Loss: ([0-9.eE+naninf-]+) Acc: ([0-9.eE+naninf-]+)"
 
 
+# (tests/mirror_gpu.py's mkargs with batchnorm on, no dropout, verbose, and the checkpoint arguments)
 def mkargs(**kw):
     a = dict(vid_len=(8, 32), num_outputs=60, drpt=0.0, inner_representation_size=16, batchnorm=True,
              alphas=False, multitask=False, weightsharing=False, batchsize=16, eta_max=1e-3, eta_min=1e-6,
@@ -110,6 +111,7 @@ class Factory:
         return m
 
 
+# (tests/mirror_gpu.py's loaders takes a train and a dev table; this one any {split: table}, float32 and unshuffled)
 def loaders(tabs, dev, B):
     import mfas_amd as M
     return {k: M.FeatureLoader(M.FeatureTable.from_numpy(t, dev, torch.float32), B, shuffle=False) for k, t in tabs.items()}

@@ -18,19 +18,12 @@ torch = pytest.importorskip("torch")
 from oracle import np_oracle as O
 from tests import surr64 as S
 from tests.helpers import golden
+from tests.surr_cases import CASES, RATIOS
+from tests.gpu_dev import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-TILE_NS = (1, 15, 17, 65)        # 16-row tiles: a lone row, a tile minus one, a tile plus one, several tiles and a ragged one
-CASES = [(H, i, E, L, n) for (H, i, E) in S.SHAPES for L in (1, 2, 4) for n in TILE_NS]
 FLOOR = 2.0 ** -20
-RATIOS = {}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "needs a HIP device"
-    return torch.device("cuda:0")
 
 
 class Engine:

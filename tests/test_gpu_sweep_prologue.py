@@ -31,6 +31,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle import np_oracle as O  # noqa: E402
+from tests.gpu_dev import dev  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -113,13 +114,6 @@ def target_build(name, nt):
     launch, a one-group plan's sweeps) take the 128-register build of the batch-tile count; four batch tiles have the one build."""
     c = CASES[name]
     return f"k_step<{c['mb']},{nt},{c['wpe']},0,1>"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -6,7 +6,8 @@ import pytest
 torch = pytest.importorskip("torch")
 from oracle import np_oracle as O
 from tests.helpers import CONFS
-from tests.test_gpu_mirror import dev, loaders, mkargs  # noqa: F401
+from tests.gpu_dev import dev  # noqa: F401
+from tests.mirror_gpu import loaders, mkargs
 
 pytestmark = pytest.mark.gpu
 

@@ -16,6 +16,7 @@ from tests.helpers import CONFS, golden
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# (tests/mirror_gpu.py's mkargs with batchnorm on and two epochs)
 def mkargs(**kw):
     a = dict(vid_len=(8, 32), num_outputs=60, drpt=0.5, inner_representation_size=16, batchnorm=True,
              alphas=False, multitask=False, weightsharing=False, batchsize=16, eta_max=1e-3, eta_min=1e-6,
@@ -129,6 +130,40 @@ def test_product_never_imports_oracle():
             if f.endswith((".py", ".hip", ".h")):
                 src = open(os.path.join(root, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle", src, re.M), f
+
+
+CASE_MODULES = ("ref64_cases", "train_cases", "wide_cases", "wide_oracle32", "resident_cases", "step_build_cases", "axes_cases",
+                "oracle32_runs", "input_cases", "evaluate_cases", "evaluate_report_cases", "report_cases", "surr_cases", "golden_cases",
+                "avmnist_cases", "pool_cases")
+
+
+def test_nothing_imports_a_test_module():
+    """What two files share lives in a support module (tests/<name>.py, no test_ prefix): no import under tests/ and tools/, function-level
+    and relative ones included, names a test module; and the case modules import neither torch nor the engine at any level."""
+    import ast
+    seen = set()
+    for top in ("tests", "tools"):
+        for root, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if not f.endswith(".py"):
+                    continue
+                path = os.path.join(root, f)
+                case_module = root == os.path.join(ROOT, "tests") and f[:-3] in CASE_MODULES
+                seen.add(f[:-3] if case_module else None)
+                for node in ast.walk(ast.parse(open(path).read(), path)):
+                    if isinstance(node, ast.Import):
+                        named, ours = [a.name for a in node.names], False
+                    elif isinstance(node, ast.ImportFrom):
+                        base = node.module or ""            # ("" in `from . import x`)
+                        named, ours = [base] + [f"{base}.{a.name}" for a in node.names], node.level > 0
+                    else:
+                        continue
+                    for m in named:
+                        parts = m.split(".")
+                        if ours or parts[0] == "tests":
+                            assert not any(p.startswith("test_") for p in parts), (path, node.lineno, m)
+                        assert not (case_module and parts[0] in ("torch", "mfas_amd")), (path, node.lineno, m)
+    assert seen - {None} == set(CASE_MODULES), set(CASE_MODULES) - seen
 
 
 def test_scheduler_matches_reference_golden():

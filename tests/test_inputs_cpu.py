@@ -1,6 +1,6 @@
 """CPU side of the value-domain tests (tests/test_gpu_inputs_ref64.py judges the kernels on the GPU):
 
-* INPUT_CASES: (base case of test_gpu_ref64.CASES or test_gpu_wide_ref64.WIDE_CASES, transform of tests/input_edges.py, table
+* INPUT_CASES: (base case of ref64_cases.CASES or wide_cases.WIDE_CASES, transform of tests/input_edges.py, table
   dtype) — a covering design, checked by test_input_cases_cover_the_design;
 * calibration: on exactly the inputs the GPU test uses, the float32 oracle stays under a quarter of every existing tau (no tau
   changes, none per case), the counts lie inside [lo, hi], and ref64 marks at most a quarter of the rows of any pass ambiguous;
@@ -41,73 +41,15 @@ import pytest
 from oracle import np_oracle as O
 from tests import input_edges as IE
 from tests import ref64 as R64
-from tests import test_gpu_ref64 as G
-from tests import test_gpu_train_ref64 as GT
-from tests import test_gpu_wide_ref64 as GW
-from tests.test_ref64_cpu import TAUS, oracle_case, oracle_train_steps
-from tests.test_wide_cpu import wide_oracle_case
+from tests import ref64_cases as G
+from tests import train_cases as GT
+from tests import wide_cases as GW
+from tests.oracle32_runs import TAUS, oracle_case, oracle_train_steps
+from tests.wide_oracle32 import wide_oracle_case
+from tests.input_cases import (EXTRA_CASES, FLAGGED, INPUT_CASES, INPUT_IDS, INPUT_SEED0, POP_CASES, base_case, entry_flag, entry_seed,
+                               flagged, is_wide, make_edit)
 
 F32 = np.float32
-INPUT_SEED0 = 7100
-F, B16, H = "float32", "bfloat16", "float16"
-
-# (base case id, how, table dtype)
-INPUT_CASES = [
-    ("r16a", "scaled", F), ("r33a", "scaled", B16), ("r32a", "scaled", H), ("r256b", "scaled", B16),
-    ("r16b", "tiny", B16), ("r17a", "tiny", F), ("r32a", "tiny", H), ("r448a", "tiny", F),
-    ("r16b", "sparse", H), ("r80a", "sparse", B16), ("r33a", "sparse", F), ("r129a", "sparse", B16),
-    ("r16a", "offset", B16), ("r32a", "offset", F), ("r80b", "offset", H), ("r33a", "offset", H),
-    ("r16a", "dup", H), ("r65a", "dup", F), ("r17a", "dup", B16), ("r129a", "dup", H),
-    ("r16b", "onelabel", F), ("r33a", "onelabel", B16), ("r32a", "onelabel", H), ("r256a", "onelabel", B16),
-    ("r16b", "dead", B16), ("r129a", "dead", F), ("r33a", "dead", H), ("r17b", "dead", H),
-    ("r16a", "bighead", B16), ("r33a", "bighead", F), ("r256a", "bighead", H), ("r65b", "bighead", F),
-    ("r17a", "mlrows", H), ("r80a", "mlrows", F), ("r129b", "mlrows", B16),
-    ("w256", "bighead", H),
-    # a ReLU FIRST cell under BatchNorm in every one: the two halves of 'dead' apart, and identical rows on the wide path
-    ("l16c", "deadrelu", F), ("r16a", "deadrelu", B16), ("r32a", "deadrelu", H), ("r256a", "deadrelu", F), ("w65", "deadrelu", H),
-    ("l16c", "bigmean", B16), ("r16a", "bigmean", H), ("r32a", "bigmean", F), ("r256a", "bigmean", B16), ("w65", "bigmean", B16),
-    ("w65", "dup", F),
-]
-INPUT_IDS = [f"{c}-{how}-{ {F: 'f32', B16: 'bf16', H: 'f16'}[dt]}" for c, how, dt in INPUT_CASES]
-
-
-# Entries judged with ref64's batch_sum_term (tests/ref64.py::forward): a column of n values near one number, whose float32 batch
-# sum rounds by more than M_mu = mean(M_a) counts.  'deadrelu' needs none (a column of exact zeros sums exactly).
-def flagged(cid, how):
-    return how == "bigmean" or (how == "dup" and cid == "w65")
-
-
-FLAGGED = {i for i, (c, how, dt) in zip(INPUT_IDS, INPUT_CASES) if flagged(c, how)}
-
-# Base cases of this file alone, where neither CASES nor WIDE_CASES has what a family needs.  The lean chain (one row block, at
-# most two m-blocks, C <= 64) has two BatchNorm cases there: r16b, whose first cell is a sigmoid, and r1a, whose single column
-# leaves 'bigmean' nothing to set (R = 1 has no r = 1 mod 3).  (r16a, B = 33, runs the general chain at four m-blocks.)
-EXTRA_CASES = {"l16c": ("l16c", 16, 17, 20, G.W_B, [[1, 0, 0], [0, 2, 1]], True, 0.5, "")}
-
-
-def entry_flag(i):
-    return INPUT_IDS[i] in FLAGGED
-
-
-def is_wide(cid):
-    return cid in GW.WIDE_IDS
-
-
-def base_case(cid, dtype=None):
-    """The 9-tuple of test_gpu_ref64's helpers for a base id; for a wide id, the wide 10-tuple with the entry's table dtype."""
-    if is_wide(cid):
-        c = GW.WIDE_CASES[GW.WIDE_IDS.index(cid)]
-        return c[:9] + (dtype or c[9],)
-    return EXTRA_CASES[cid] if cid in EXTRA_CASES else G.CASES[G.CASE_IDS.index(cid)]
-
-
-# Entries whose draw at INPUT_SEED0 + i leaves more than a quarter of a train batch ambiguous: the first seed from 7200 on at which
-# ref64 alone meets every condition of entry_ratios (and the float32 oracle its calibration margin).
-SEED_OVERRIDE = {"r32a-scaled-f16": 7200, "r80a-sparse-bf16": 7211, "r256a-bighead-f16": 7200}
-
-
-def entry_seed(i):
-    return SEED_OVERRIDE.get(INPUT_IDS[i], INPUT_SEED0 + i)
 
 
 def ambiguity_exempt(cid, how, hp):
@@ -116,17 +58,6 @@ def ambiguity_exempt(cid, how, hp):
     transforms that take a column's batch variance towards 0 ('dup', 'offset', 'dead', 'deadrelu': rstd up to 1 / sqrt(eps) =
     316) or that are judged with the batch-sum term ('bigmean': M_mu of the +64 columns is 64 (n - 1))."""
     return hp.bn and (cid == "r16b" or how in ("dup", "offset", "dead", "deadrelu", "bigmean"))
-
-
-def make_edit(how):
-    """The hook oracle_case / oracle_train_steps / the GPU test pass their inputs through."""
-    def edit(conf, hp, p0, t, dtype):
-        p = IE.edge_params(p0, hp, conf, how)
-        top = None
-        if how == "mlrows":
-            top = int(np.argmax(R64.forward(p, conf, hp, G.feats_of(t, 4, 1), False)[0][0]))
-        return p, IE.edge_table(t, how, dtype, C=hp.C, top=top)
-    return edit
 
 
 def ambiguous_rows(lo, hi, n, hp):
@@ -275,7 +206,7 @@ def test_input_cases_cover_the_design():
     assert all(is_wide(c) or c in G.CASE_IDS or c in EXTRA_CASES for c in ids)
     # BatchNorm and a ReLU first cell in every entry of the two halves of 'dead' and in the wide 'dup'; every BatchNorm transcription
     # under each half: the lean chain (resident at one candidate), the general chain at 1 / 2 / 4 m-blocks, R >= 256, the wide path
-    from tests.test_wide_cpu import plan
+    from tests.wide_plans import plan
     for how in ("deadrelu", "bigmean"):
         mine = [(c, base_case(c)) for c, h, _ in INPUT_CASES if h == how]
         assert all(bc[6] and bc[5][0][2] == 0 for _, bc in mine), how
@@ -293,18 +224,10 @@ def test_input_cases_cover_the_design():
         assert plan(G.case_hyper(bc), [bc[5]])[5] == 1 and cid not in G.CASE_IDS, cid
 
 
-# (schedule of test_gpu_train_ref64.TRAIN_SCHEDULES, transform of one candidate's parameters, that candidate): the resident
-# schedule, chain_split and launch per phase.  'dead' goes to a candidate whose first cell is a sigmoid (its +64 half on a ReLU
-# first cell needs ref64's batch-sum term), 'deadrelu' to one whose first cell is a ReLU: on the resident schedule, chain_split, the
-# same-group launch of the general chain, and the lean chain launched per phase.
-POP_CASES = [("persistent", "dead", 3), ("chain_split", "bighead", 1), ("lean_chain", "bighead", 2),
-             ("persistent", "deadrelu", 0), ("chain_split", "deadrelu", 0), ("same_group", "deadrelu", 0), ("lean_chain", "deadrelu", 0)]
-
-
 @pytest.mark.parametrize("name,how,k", POP_CASES, ids=[f"{n}-{h}" for n, h, _ in POP_CASES])
 def test_population_cases_calibration_margin(name, how, k):
     """The transformed candidate of each population case: the float32 oracle under a quarter of every tau on steps 1..3."""
-    from tests.test_ref64_cpu import oracle_steps
+    from tests.oracle32_runs import oracle_steps
     inp = GT.schedule_inputs(name, "shared")
     hp, conf = inp["hp"], inp["confs"][k]
     assert how != "dead" or int(conf[0][2]) == 1
@@ -711,7 +634,7 @@ def test_mutation_negative_zero_read_as_a_value(cid):
 
 def test_rne_bf16_reference_of_the_pool_test():
     """The rounding reference of tests/test_gpu_pool_ref64.py: float64 -> bf16 in one rounding, ties to even."""
-    from tests.test_gpu_pool_ref64 import rne16, rne_bf16
+    from tests.pool_cases import rne16, rne_bf16
     one, ulp = 1.0, 2.0 ** -7
     assert rne_bf16(one + 0.5 * ulp) == one and rne_bf16(one + 1.5 * ulp) == one + 2 * ulp
     assert rne_bf16(one + 0.5 * ulp + 2.0 ** -40) == one + ulp          # (a float32 step in between would have made it a tie)

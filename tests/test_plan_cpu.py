@@ -17,12 +17,12 @@ import numpy as np
 
 from oracle import np_oracle as O
 from tests import builds_header as BH
-from tests import test_axes_cpu as AX
-from tests import test_gpu_ref64 as G
-from tests import test_gpu_resident_ref64 as GR
-from tests import test_gpu_wide_ref64 as GW
-from tests import test_step_builds_cpu as SB
-from tests import test_wide_cpu as TW
+from tests import axes_cases as AX
+from tests import ref64_cases as G
+from tests import resident_cases as GR
+from tests import wide_cases as GW
+from tests import step_build_cases as SB
+from tests import wide_plans as TW
 from tests.helpers import CONFS, engine_hyper
 
 GRID_SEED = 20261

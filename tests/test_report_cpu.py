@@ -17,8 +17,8 @@ import pytest
 from oracle import np_oracle as O
 from tests import builds_header as BH
 from tests import ref64 as R64
-from tests import test_gpu_ref64 as G
-from tests import test_gpu_report_ref64 as RP
+from tests import gpu_support as G
+from tests import report_cases as RP
 
 F32 = np.float32
 

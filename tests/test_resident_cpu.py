@@ -13,11 +13,11 @@ import numpy as np
 import pytest
 
 from tests import builds_header as BH
-from tests import test_gpu_ref64 as G
-from tests import test_gpu_resident_ref64 as GR
-from tests import test_gpu_train_ref64 as GT
-from tests import test_gpu_wide_ref64 as GW
-from tests.test_ref64_cpu import MUT_CE, oracle_steps, oracle_train_steps
+from tests import ref64_cases as G
+from tests import resident_gpu as GR
+from tests import train_cases as GT
+from tests import wide_cases as GW
+from tests.oracle32_runs import MUT_CE, oracle_steps, oracle_train_steps
 
 WORST = {}          # group -> {quantity: worst ratio of the float32 oracle}
 

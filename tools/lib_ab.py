@@ -44,9 +44,9 @@ SCHED_CASES = {
     # host-bound: the lean chain launch per phase (R = 16, B = 20, MFAS_PERSIST=0), one group, chain + sweep = two launches per step
     "lean_per_phase": ("lean_chain", None, {}),
 }
-# single-candidate cases of test_gpu_ref64.CASES (general chain: more than 64 classes, alphas, multi-label, multitask, no BatchNorm)
+# single-candidate cases of ref64_cases.CASES (general chain: more than 64 classes, alphas, multi-label, multitask, no BatchNorm)
 ENVELOPE_CASES = ("r17a", "r32a", "r33a", "r65b", "r80a", "r128a", "r128b")
-# test_gpu_wide_ref64.WIDE_CASES: B > 64, R > 128, every head, alphas
+# wide_cases.WIDE_CASES: B > 64, R > 128, every head, alphas
 WIDE = ("wb65", "wb128", "w177", "w256", "w80", "wc")
 
 
@@ -54,9 +54,9 @@ def run_case(name, dev, reps):
     """-> (sha256 over planes / statistics / status, schedule, best seconds of a train() call)"""
     import numpy as np
     import torch
-    from tests import test_gpu_ref64 as G
-    from tests import test_gpu_train_ref64 as GT
-    from tests import test_gpu_wide_ref64 as GW
+    from tests import gpu_support as G
+    from tests import train_gpu as GT
+    from tests import wide_gpu as GW
     if name in SCHED_CASES:
         base, entry, edits = SCHED_CASES[name]
         entry = entry or GT.TRAIN_SCHEDULES[base]
