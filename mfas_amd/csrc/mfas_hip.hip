@@ -17,7 +17,8 @@
 // Source layout (ONE translation unit; this file includes the rest): common.hip.h (device records, helpers, LDS staging), sweep.hip.h
 // (tile_run, sweep_body, sweep_tap_body), chain.hip.h (chain_body, chain_lean, softmax / BCE rows), wide.hip.h (k_chain_wide / k_sweep_wide:
 // the batch walked in tiles), eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe), surrogate.hip.h (the search
-// controller's LSTM surrogate: k_surr_grad / k_surr_adam / k_surr_forward and their stateless C ABI); host only: plan.hip.h (the switches,
+// controller's LSTM surrogate: k_surr_grad / k_surr_adam / k_surr_forward and their stateless C ABI); host only: devmem.hip.h (DevBuf: the
+// one owner of device memory — a population's buffers and every call's scratch free themselves; nothing else allocates or frees), plan.hip.h (the switches,
 // validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated; plan_dump.hip.h: the
 // plan as text, test-hooks variant only), launches.hip.h (the
 // launches of an epoch as data), builds.hip.h (which build a launch takes, as data: the choice functions, the builds a plan can launch, the
@@ -41,7 +42,9 @@
 #include <math.h>
 #include <cmath>
 #include <algorithm>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 #include <thread>
 #include <chrono>
@@ -117,6 +120,7 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
 #include "pack.hip.h"
 #include "surrogate.hip.h"
 
+#include "devmem.hip.h"
 #include "builds.hip.h"
 #include "plan.hip.h"
 #ifdef MFAS_TEST_HOOKS
@@ -148,6 +152,33 @@ struct LaunchRecord {
     }
 };
 
+// The profiling event pairs of a population.  Move-only, and a move EXCHANGES: whichever record, or temporary of a swap, ends up
+// holding an event destroys it, once.
+struct EventPairs {
+    std::vector<hipEvent_t> v;
+    EventPairs() = default;
+    EventPairs(EventPairs&& o) noexcept { v.swap(o.v); }
+    EventPairs& operator=(EventPairs&& o) noexcept {
+        v.swap(o.v);
+        return *this;
+    }
+    ~EventPairs() {
+        for (hipEvent_t e : v) hipEventDestroy(e);
+    }
+    // one more pair; false, and nothing added, when an event cannot be created
+    bool add_pair() {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (hipEventCreate(&e0) != hipSuccess) return false;
+        if (hipEventCreate(&e1) != hipSuccess) {
+            hipEventDestroy(e0);
+            return false;
+        }
+        v.push_back(e0);
+        v.push_back(e1);
+        return true;
+    }
+};
+
 struct mfas_population {
     mfas_hyper hp;
     Tuning tune;                    // the environment switches as they stood when the population was created
@@ -155,24 +186,22 @@ struct mfas_population {
     int chunk_cols_req = 0;         // chunk_cols the caller asked for at creation (the fallback layout is built with the same request)
     hipStream_t stream = nullptr;
     LayoutPlan plan;                // layout, schedule, LDS budgets, work lists (plan.hip.h): decided before anything was allocated, never changed
-    float* plane = nullptr;
-    float* wt = nullptr;
-    float* stepbuf = nullptr;
-    float* best = nullptr;          // snapshot_best: copy of plane 0
-    CandDev* d_cands = nullptr;
-    SegDesc* d_descs = nullptr;
-    struct GroupDev { SegDesc* d_descs = nullptr; TapDesc* d_taps = nullptr; };
+    // device memory: every buffer owns itself (devmem.hip.h) — nothing here is freed by hand, a grow-only buffer's capacity is its size()
+    DevBuf<float> plane, wt, stepbuf;
+    DevBuf<float> best;             // snapshot_best: copy of plane 0 (keep_best, state.hip.h)
+    DevBuf<CandDev> d_cands;
+    DevBuf<SegDesc> d_descs;
+    struct GroupDev { DevBuf<SegDesc> d_descs; DevBuf<TapDesc> d_taps; };
     std::vector<GroupDev> groups;   // device copies of plan.groups[i].descs / .taps
-    DevStats* d_stats = nullptr;
-    int32_t* d_status = nullptr;
-    uint32_t* d_seeds = nullptr;
-    long long* d_corr = nullptr;
-    float* d_posw = nullptr;        // loss_mode 1: per-class positive weights (default 1)
-    int stats_cap = 0;
+    DevBuf<DevStats> d_stats;       // [K][epochs] of the largest schedule so far (grow-only)
+    DevBuf<int32_t> d_status;
+    DevBuf<uint32_t> d_seeds;
+    DevBuf<long long> d_corr;
+    DevBuf<float> d_posw;           // loss_mode 1: per-class positive weights (default 1)
     // profiling of the dominant kernel
     bool profiling = false;
     int prof_every = 16;            // HIP events bracket every prof_every-th sweep launch (event records are not free)
-    std::vector<hipEvent_t> ev;     // pairs
+    EventPairs ev;
     int64_t prof_launches = 0;
     double prof_ms = 0.0, bytes_per_launch = 0.0, prof_bytes = 0.0;
     LaunchRecord launched;          // the builds the last train call launched (cleared when a call has passed its checks)
@@ -186,24 +215,28 @@ struct mfas_population {
         std::vector<int32_t> keeps_best;    // the schedule runs with snapshot_best: plane `best` holds this candidate's best epoch
         void reset(int K, double threshold) { done.assign(K, 0); nb.assign(K, 0); best_metric.assign(K, threshold); keeps_best.assign(K, 0); }
     } prog;
-    float* d_move = nullptr;        // mfas_population_move: one candidate in flat state_dict order (grow-only scratch of the destination)
-    int64_t move_cap = 0;
-    uint32_t* d_red_cnt = nullptr;  // reduce-in-sweep arrival counters [K][4] (small populations, general chain)
-    char* d_gather = nullptr;       // gathered rows [K][2 parities][taps][Bp][width] (two-group schedule, per-candidate orders; sweep.hip.h)
-    size_t gather_cap = 0;
-    uint32_t* d_cellflag = nullptr; // [K][CELLFLAG_STRIDE]
-    float* d_xch = nullptr;         // chain_split's exchange area [K][XCH_CAND_FLOATS]
+    DevBuf<float> d_move;           // mfas_population_move: one candidate in flat state_dict order (grow-only scratch of the destination)
+    DevBuf<uint32_t> d_red_cnt;     // reduce-in-sweep arrival counters [K][4] (small populations, general chain)
+    DevBuf<char> d_gather;          // gathered rows [K][2 parities][taps][Bp][width] (two-group schedule, per-candidate orders; sweep.hip.h; grow-only)
+    DevBuf<uint32_t> d_cellflag;    // [K][CELLFLAG_STRIDE]
+    DevBuf<float> d_xch;            // chain_split's exchange area [K][XCH_CAND_FLOATS]
     // persistent step loop (persist.hip.h)
-    SegDesc* d_pdescs = nullptr;    // plan.pdescs
+    DevBuf<SegDesc> d_pdescs;       // plan.pdescs
     int fell_back = 0;              // the resident schedule was given up for launch-per-phase inside a train() call (roll call never complete)
-    uint32_t* d_sync = nullptr;     // [K] flags | [K] counters | abort word (zeroed before every launch)
-    int32_t* d_need = nullptr;      // plan.need
-    int32_t* d_role = nullptr;      // plan.role
-    float* d_scal = nullptr;        // device copy of the step scalars
-    size_t scal_cap = 0;
-    unsigned long long* d_trace = nullptr;
-    char* d_vote = nullptr;         // mfas_population_evaluate's arena (grow-only; vote.hip.h): nothing a train call reads
-    size_t vote_cap = 0;
+    DevBuf<uint32_t> d_sync;        // [K] flags | [K] counters | abort word (zeroed before every launch)
+    DevBuf<int32_t> d_need, d_role; // plan.need, plan.role
+    DevBuf<float> d_scal;           // device copy of the step scalars (grow-only)
+    DevBuf<unsigned long long> d_trace;
+    DevBuf<char> d_vote;            // mfas_population_evaluate's arena (grow-only; vote.hip.h): nothing a train call reads
+
+    mfas_population() = default;
+    mfas_population(mfas_population&&) = default;               // (persist_fallback swaps two records; the temporary of that swap
+    mfas_population& operator=(mfas_population&&) = default;    //  waits for the — drained — stream too when it leaves)
+    // what the stream still runs may read the buffers: wait for it, then the members free themselves
+    ~mfas_population() {
+        hipSetDevice(device);
+        hipStreamSynchronize(stream);
+    }
 };
 
 // roctx ranges around a train() call and each of its epochs (rocprofv3 --marker-trace shows them next to the kernels).  The
@@ -351,14 +384,7 @@ static int device_cus(int device) {
     return ncu;
 }
 
-template <typename T>
-static hipError_t upload(T** dst, const std::vector<T>& v) {      // (an empty list stays a null pointer)
-    if (v.empty()) return hipSuccess;
-    hipError_t e = hipMalloc(dst, sizeof(T) * v.size());
-    return e != hipSuccess ? e : hipMemcpy(*dst, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
-}
-
-// validate -> plan (pure: plan.hip.h) -> allocate / upload / set the LDS limits from the plan; one error path that frees what was allocated
+// validate -> plan (pure: plan.hip.h) -> allocate / upload / set the LDS limits from the plan; a failure on the way just leaves: the record owns its buffers
 static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells,
                        const uint32_t* drop_seeds, int32_t K, int32_t device, void* hip_stream,
                        int32_t chunk_cols, mfas_population** out, const bool allow_persist, const Tuning* inherit = nullptr) {
@@ -366,7 +392,7 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
     if (int vrc = validate_inputs(hp, confs, n_cells, K)) return vrc;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return fail(MFAS_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    mfas_population* p = new (std::nothrow) mfas_population();
+    std::unique_ptr<mfas_population> p(new (std::nothrow) mfas_population());
     if (!p) return fail(MFAS_ENOMEM, "host alloc");
     p->hp = *hp;
     p->tune = inherit ? *inherit : tuning_from_env();      // (persist_fallback rebuilds a population under the switches it was created with)
@@ -376,59 +402,57 @@ static int create_impl(const mfas_hyper* hp, const int32_t* confs, const int32_t
     p->chunk_cols_req = chunk_cols;
     p->n_cus = device_cus(device);
     p->prog.reset(K, 0.0);
-    if (int prc = plan_layout(hp, confs, n_cells, drop_seeds, K, chunk_cols, p->n_cus, allow_persist, p->tune, p->plan)) { delete p; return prc; }
+    if (int prc = plan_layout(hp, confs, n_cells, drop_seeds, K, chunk_cols, p->n_cus, allow_persist, p->tune, p->plan)) return prc;
     const LayoutPlan& pl = p->plan;
-    if (!pl.fits_lds) { delete p; return fail(MFAS_EINVAL, "geometry does not fit the 160 KiB LDS (R / batchsize too large)"); }
+    if (!pl.fits_lds) return fail(MFAS_EINVAL, "geometry does not fit the 160 KiB LDS (R / batchsize too large)");
     p->bytes_per_launch = pl.bytes_per_launch;
 
 #define CREATE_CHK(x)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            std::string m_ = std::string(#x) + ": " + hipGetErrorString(e_);                       \
-            mfas_population_destroy(p);                                                            \
-            return fail(e_ == hipErrorOutOfMemory ? MFAS_ENOMEM : MFAS_EHIP, m_);                  \
-        }                                                                                          \
+        if (e_ != hipSuccess)                                                                      \
+            return fail(e_ == hipErrorOutOfMemory ? MFAS_ENOMEM : MFAS_EHIP,                       \
+                        std::string(#x) + ": " + hipGetErrorString(e_));                           \
     } while (0)
-    const size_t wt_floats = (size_t)std::max<int64_t>(pl.wt_size, 64);
-    CREATE_CHK(hipMalloc(&p->plane, sizeof(float) * 3 * (size_t)pl.plane_stride));
-    CREATE_CHK(hipMalloc(&p->wt, sizeof(float) * wt_floats));
-    CREATE_CHK(hipMalloc(&p->stepbuf, sizeof(float) * (size_t)pl.step_total));
-    CREATE_CHK(hipMalloc(&p->d_status, sizeof(int32_t) * (K + 256)));   // + debug timestamp slots (MFAS_CHAIN_TIMING builds)
-    CREATE_CHK(hipMemset(p->d_status, 0, sizeof(int32_t) * (K + 256)));
-    CREATE_CHK(hipMalloc(&p->d_seeds, sizeof(uint32_t) * K));
-    CREATE_CHK(hipMalloc(&p->d_corr, sizeof(long long)));
-    CREATE_CHK(upload(&p->d_posw, std::vector<float>(pl.g.Cp, 1.0f)));
-    CREATE_CHK(upload(&p->d_cands, pl.cands));
-    CREATE_CHK(upload(&p->d_descs, pl.descs));
+    const size_t wt_floats = (size_t)std::max<int64_t>(pl.wt_size, 64), nstatus = (size_t)K + 256, nred = (size_t)K * MFAS_MAX_CELLS;
+    CREATE_CHK(p->plane.alloc(3 * (size_t)pl.plane_stride));
+    CREATE_CHK(p->wt.alloc(wt_floats));
+    CREATE_CHK(p->stepbuf.alloc((size_t)pl.step_total));
+    CREATE_CHK(p->d_status.alloc(nstatus));   // + debug timestamp slots (MFAS_CHAIN_TIMING builds)
+    CREATE_CHK(hipMemset(p->d_status.get(), 0, sizeof(int32_t) * nstatus));
+    CREATE_CHK(p->d_seeds.alloc(K));
+    CREATE_CHK(p->d_corr.alloc(1));
+    CREATE_CHK(p->d_posw.upload(std::vector<float>(pl.g.Cp, 1.0f)));
+    CREATE_CHK(p->d_cands.upload(pl.cands));
+    CREATE_CHK(p->d_descs.upload(pl.descs));
     p->groups.resize(pl.groups.size());
     for (size_t gi = 0; gi < pl.groups.size(); ++gi) {
-        CREATE_CHK(upload(&p->groups[gi].d_descs, pl.groups[gi].descs));
-        CREATE_CHK(upload(&p->groups[gi].d_taps, pl.groups[gi].taps));
+        CREATE_CHK(p->groups[gi].d_descs.upload(pl.groups[gi].descs));
+        CREATE_CHK(p->groups[gi].d_taps.upload(pl.groups[gi].taps));
     }
     if (pl.red_in_sweep) {
-        CREATE_CHK(hipMalloc(&p->d_red_cnt, sizeof(uint32_t) * K * MFAS_MAX_CELLS));
-        CREATE_CHK(hipMemset(p->d_red_cnt, 0, sizeof(uint32_t) * K * MFAS_MAX_CELLS));
+        CREATE_CHK(p->d_red_cnt.alloc(nred));
+        CREATE_CHK(hipMemset(p->d_red_cnt.get(), 0, sizeof(uint32_t) * nred));
     }
-    if (pl.same_group) CREATE_CHK(hipMalloc(&p->d_cellflag, sizeof(uint32_t) * K * CELLFLAG_STRIDE));
-    if (pl.chain_split) CREATE_CHK(hipMalloc(&p->d_xch, sizeof(float) * (size_t)K * XCH_CAND_FLOATS));
-    CREATE_CHK(hipMemsetAsync(p->plane, 0, sizeof(float) * 3 * (size_t)pl.plane_stride, p->stream));
-    CREATE_CHK(hipMemsetAsync(p->wt, 0, sizeof(float) * wt_floats, p->stream));
-    CREATE_CHK(hipMemsetAsync(p->stepbuf, 0, sizeof(float) * (size_t)pl.step_total, p->stream));
+    if (pl.same_group) CREATE_CHK(p->d_cellflag.alloc((size_t)K * CELLFLAG_STRIDE));
+    if (pl.chain_split) CREATE_CHK(p->d_xch.alloc((size_t)K * XCH_CAND_FLOATS));
+    CREATE_CHK(hipMemsetAsync(p->plane.get(), 0, sizeof(float) * 3 * (size_t)pl.plane_stride, p->stream));
+    CREATE_CHK(hipMemsetAsync(p->wt.get(), 0, sizeof(float) * wt_floats, p->stream));
+    CREATE_CHK(hipMemsetAsync(p->stepbuf.get(), 0, sizeof(float) * (size_t)pl.step_total, p->stream));
     CREATE_CHK(set_lds_all(pl));
     if (pl.persist) {
-        CREATE_CHK(upload(&p->d_pdescs, pl.pdescs));
-        CREATE_CHK(upload(&p->d_need, pl.need));
-        CREATE_CHK(upload(&p->d_role, pl.role));
-        CREATE_CHK(hipMalloc(&p->d_sync, sizeof(uint32_t) * ((size_t)K * PERSIST_SYNC_STRIDE + 64)));
+        CREATE_CHK(p->d_pdescs.upload(pl.pdescs));
+        CREATE_CHK(p->d_need.upload(pl.need));
+        CREATE_CHK(p->d_role.upload(pl.role));
+        CREATE_CHK(p->d_sync.alloc((size_t)K * PERSIST_SYNC_STRIDE + 64));
         if (p->tune.persist_trace) {
-            CREATE_CHK(hipMalloc(&p->d_trace, sizeof(unsigned long long) * 256));
-            CREATE_CHK(hipMemset(p->d_trace, 0, sizeof(unsigned long long) * 256));
+            CREATE_CHK(p->d_trace.alloc(256));
+            CREATE_CHK(hipMemset(p->d_trace.get(), 0, sizeof(unsigned long long) * 256));
         }
     }
     CREATE_CHK(hipStreamSynchronize(p->stream));
 #undef CREATE_CHK
-    *out = p;
+    *out = p.release();
     return MFAS_OK;
 }
 
@@ -453,24 +477,7 @@ extern "C" int mfas_population_plan(const mfas_hyper* hp, const int32_t* confs, 
     return MFAS_OK;
 }
 
-extern "C" void mfas_population_destroy(mfas_population* p) {
-    if (!p) return;
-    hipSetDevice(p->device);
-    hipStreamSynchronize(p->stream);
-    for (hipEvent_t e : p->ev) hipEventDestroy(e);
-    hipFree(p->plane); hipFree(p->wt); hipFree(p->stepbuf); hipFree(p->best);
-    for (auto& gr : p->groups) { hipFree(gr.d_descs); hipFree(gr.d_taps); }
-    hipFree(p->d_cands); hipFree(p->d_descs); hipFree(p->d_stats); hipFree(p->d_status);
-    hipFree(p->d_seeds); hipFree(p->d_corr); hipFree(p->d_posw);
-    hipFree(p->d_red_cnt);
-    hipFree(p->d_gather);
-    hipFree(p->d_cellflag);
-    hipFree(p->d_xch);
-    hipFree(p->d_move);
-    hipFree(p->d_vote);
-    hipFree(p->d_sync); hipFree(p->d_need); hipFree(p->d_role); hipFree(p->d_scal); hipFree(p->d_trace); hipFree(p->d_pdescs);
-    delete p;
-}
+extern "C" void mfas_population_destroy(mfas_population* p) { if (p) delete p; }      // (~mfas_population waits for the stream)
 
 extern "C" int64_t mfas_population_param_count(const mfas_population* p, int32_t k) {
     if (!p || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad candidate index");
@@ -521,7 +528,7 @@ static hipError_t launch_eval(mfas_population* p, const EvalArgs& a, int ncand, 
 extern "C" int mfas_population_set_params(mfas_population* p, int32_t k, const float* flat) {
     if (!p || !flat || k < 0 || k >= p->K) return fail(MFAS_EINVAL, "bad argument");
     HIPCHK(hipSetDevice(p->device));
-    put_plane(p, k, p->plane, 0, PK_SET, true, flat, p->stream);
+    put_plane(p, k, p->plane.get(), 0, PK_SET, true, flat, p->stream);
     HIPCHK(hipGetLastError());
     return MFAS_OK;
 }
@@ -531,7 +538,7 @@ extern "C" int mfas_population_get_params(mfas_population* p, int32_t k, int32_t
     if (plane == 3 && !(p->best && p->prog.keeps_best[k]))
         return fail(MFAS_EINVAL, "plane 3: candidate " + std::to_string(k) + " keeps no best-epoch parameters (no snapshot_best schedule in progress)");
     HIPCHK(hipSetDevice(p->device));
-    HIPCHK(get_plane(p, k, plane == 3 ? p->best : p->plane, plane == 3 ? 0 : plane, flat, p->stream));
+    HIPCHK(get_plane(p, k, plane == 3 ? p->best.get() : p->plane.get(), plane == 3 ? 0 : plane, flat, p->stream));
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(p->stream));
     return MFAS_OK;
@@ -540,7 +547,7 @@ extern "C" int mfas_population_get_params(mfas_population* p, int32_t k, int32_t
 extern "C" int mfas_population_init(mfas_population* p, const uint32_t* seeds) {
     if (!p || !seeds) return fail(MFAS_EINVAL, "bad argument");
     HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpyAsync(p->d_seeds, seeds, sizeof(uint32_t) * p->K, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(p->d_seeds.get(), seeds, sizeof(uint32_t) * p->K, hipMemcpyHostToDevice, p->stream));
     run_pack(p, pack_args(p, PK_INIT, 0, nullptr), -1, true, p->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(p->stream));   // seeds is a host buffer
@@ -553,10 +560,10 @@ extern "C" int mfas_population_set_state(mfas_population* p, int32_t k, int32_t 
         return fail(MFAS_EINVAL, "set_state: plane " + std::to_string(plane) + " (1 = exp_avg, 2 = exp_avg_sq, 3 = kept best; plane 0 is mfas_population_set_params)");
     HIPCHK(hipSetDevice(p->device));
     if (plane == 3) {
-        if (int rc = ensure_best(p, p->stream)) return rc;
-        put_plane(p, k, p->best, 0, PK_PUT, false, flat, p->stream);
+        HIPCHK(keep_best(p, BEST_LIVE_IF_NEW, p->stream));
+        put_plane(p, k, p->best.get(), 0, PK_PUT, false, flat, p->stream);
         p->prog.keeps_best[k] = 1;
-    } else put_plane(p, k, p->plane, plane, PK_PUT, false, flat, p->stream);
+    } else put_plane(p, k, p->plane.get(), plane, PK_PUT, false, flat, p->stream);
     HIPCHK(hipGetLastError());
     return MFAS_OK;
 }
@@ -569,7 +576,7 @@ extern "C" int mfas_population_get_progress(mfas_population* p, int32_t k, int64
     if (best_metric) *best_metric = p->prog.best_metric[k];
     if (status) {
         HIPCHK(hipSetDevice(p->device));
-        HIPCHK(hipMemcpyAsync(status, p->d_status + k, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipMemcpyAsync(status, p->d_status.get() + k, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
         HIPCHK(hipStreamSynchronize(p->stream));
     }
     return MFAS_OK;
@@ -581,7 +588,7 @@ extern "C" int mfas_population_set_progress(mfas_population* p, int32_t k, const
     if ((epochs_done && *epochs_done < 0) || (nb && *nb < 0)) return fail(MFAS_EINVAL, "set_progress: negative epoch or batch count");
     if (status) {
         HIPCHK(hipSetDevice(p->device));
-        HIPCHK(hipMemcpyAsync(p->d_status + k, status, sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
+        HIPCHK(hipMemcpyAsync(p->d_status.get() + k, status, sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
         HIPCHK(hipStreamSynchronize(p->stream));      // status is a host word
     }
     if (epochs_done) { p->prog.done[k] = *epochs_done; if (*epochs_done == 0) p->prog.keeps_best[k] = 0; }
@@ -610,18 +617,16 @@ extern "C" int mfas_population_forward(mfas_population* p, int32_t k, const mfas
     if (rc) return rc;
     if (row0 + nrows > tab->N) return fail(MFAS_EINVAL, "row range outside the table");
     HIPCHK(hipSetDevice(p->device));
-    EvalArgs ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.cands = p->d_cands; ea.plane = p->plane; ea.tab = *tab; ea.row0 = row0; ea.nrows = nrows;
-    ea.cand0 = k; ea.epoch = 0; ea.E = 1; ea.g = p->plan.g; ea.logits = logits; ea.pos_w = p->d_posw;
+    EvalArgs ea = eval_args(p, *tab, p->plane.get(), p->plan.g);
+    ea.row0 = row0; ea.nrows = nrows; ea.cand0 = k; ea.logits = logits;
     if (corrects) {
-        HIPCHK(hipMemsetAsync(p->d_corr, 0, sizeof(long long), p->stream));
-        ea.corr_out = p->d_corr;
+        HIPCHK(hipMemsetAsync(p->d_corr.get(), 0, sizeof(long long), p->stream));
+        ea.corr_out = p->d_corr.get();
     }
     HIPCHK(launch_eval(p, ea, 1, p->stream));
     if (corrects) {
         long long h = 0;
-        HIPCHK(hipMemcpyAsync(&h, p->d_corr, sizeof(long long), hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipMemcpyAsync(&h, p->d_corr.get(), sizeof(long long), hipMemcpyDeviceToHost, p->stream));
         HIPCHK(hipStreamSynchronize(p->stream));
         *corrects = (int64_t)h;
     }
@@ -658,21 +663,23 @@ extern "C" int mfas_population_backward(mfas_population* p, int32_t k, const mfa
 extern "C" int mfas_stream_probe(int64_t bytes_per_plane, int32_t iters, double* gb_per_s) {
     if (bytes_per_plane < (1 << 20) || iters < 1 || !gb_per_s) return fail(MFAS_EINVAL, "bad argument");
     const size_t plane = (size_t)bytes_per_plane / 1024 * 256;   // floats, whole tiles
-    float* P = nullptr;
-    HIPCHK(hipMalloc(&P, plane * 4 * 3));
-    hipError_t e = hipMemset(P, 0, plane * 4 * 3);
-    hipEvent_t a, b;
+    DevBuf<float> P;
+    HIPCHK(P.alloc(plane * 3));
+    hipError_t e = hipMemset(P.get(), 0, plane * 4 * 3);
+    hipEvent_t a = nullptr, b = nullptr;
     if (e == hipSuccess) e = hipEventCreate(&a);
     if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e != hipSuccess) { hipFree(P); return fail(MFAS_EHIP, hipGetErrorString(e)); }
-    hipLaunchKernelGGL(k_stream_probe, dim3(2048), dim3(256), 0, 0, P, plane, plane / 256);
-    hipEventRecord(a, 0);
-    for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(k_stream_probe, dim3(2048), dim3(256), 0, 0, P, plane, plane / 256);
-    hipEventRecord(b, 0);
-    e = hipEventSynchronize(b);
     float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
-    hipEventDestroy(a); hipEventDestroy(b); hipFree(P);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_stream_probe, dim3(2048), dim3(256), 0, 0, P.get(), plane, plane / 256);
+        hipEventRecord(a, 0);
+        for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(k_stream_probe, dim3(2048), dim3(256), 0, 0, P.get(), plane, plane / 256);
+        hipEventRecord(b, 0);
+        e = hipEventSynchronize(b);
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
+    }
+    if (a) hipEventDestroy(a);      // (both events go on every path)
+    if (b) hipEventDestroy(b);
     if (e != hipSuccess) return fail(MFAS_EHIP, hipGetErrorString(e));
     *gb_per_s = (double)plane * 4 * 3 * 2 * iters / 1e9 / (ms * 1e-3);
     return MFAS_OK;
@@ -693,7 +700,7 @@ extern "C" int mfas_global_pool(const void* x, int32_t dtype, int64_t rows, int6
 extern "C" int mfas_population_set_pos_weight(mfas_population* p, const float* w) {
     if (!p || !w) return fail(MFAS_EINVAL, "null");
     HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(p->d_posw, w, sizeof(float) * p->plan.g.C, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->d_posw.get(), w, sizeof(float) * p->plan.g.C, hipMemcpyHostToDevice));
     return MFAS_OK;
 }
 

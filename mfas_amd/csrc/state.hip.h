@@ -5,15 +5,15 @@
 static PackArgs pack_args(mfas_population* p, int mode, int plane, float* flat) {
     PackArgs a;
     memset(&a, 0, sizeof(a));
-    a.desc = p->d_descs; a.cands = p->d_cands; a.plane = p->plane; a.plane_stride = p->plan.plane_stride;
-    a.wt = p->wt; a.flat = flat; a.seeds = p->d_seeds; a.mode = mode; a.sel_plane = plane; a.g = p->plan.g;
+    a.desc = p->d_descs.get(); a.cands = p->d_cands.get(); a.plane = p->plane.get(); a.plane_stride = p->plan.plane_stride;
+    a.wt = p->wt.get(); a.flat = flat; a.seeds = p->d_seeds.get(); a.mode = mode; a.sel_plane = plane; a.g = p->plan.g;
     return a;
 }
 
 // k_pack over candidate k's descriptors + k_vec for its vector block; k < 0: every candidate's (errors: hipGetLastError)
 static void run_pack(mfas_population* p, PackArgs a, int k, bool vec, hipStream_t st) {
     const int d0 = k < 0 ? 0 : p->plan.desc_start[k], d1 = k < 0 ? (int)p->plan.descs.size() : p->plan.desc_start[k + 1];
-    a.desc = p->d_descs + d0;
+    a.desc = p->d_descs.get() + d0;
     hipLaunchKernelGGL(k_pack, dim3((unsigned)(d1 - d0)), dim3(256), 0, st, a);
     if (vec) hipLaunchKernelGGL(k_vec, dim3(k < 0 ? p->K : 1), dim3(256), 0, st, a, k);
 }
@@ -44,18 +44,25 @@ static void put_plane(mfas_population* p, int k, float* plane_base, int sel, int
 static hipError_t carry_candidate(mfas_population* dst, int kd, mfas_population* src, int ks, bool with_best, float* flat, hipStream_t st) {
     for (int i = 0; i < (with_best ? 4 : 3); ++i) {     // W (PK_SET: + the transposed images, zeroes m / v), m, v, the kept best
         const int sel = i % 3;
-        if (hipError_t e = get_plane(src, ks, i == 3 ? src->best : src->plane, sel, flat, st)) return e;
-        put_plane(dst, kd, i == 3 ? dst->best : dst->plane, sel, i == 0 ? PK_SET : PK_PUT, i == 0, flat, st);
+        if (hipError_t e = get_plane(src, ks, i == 3 ? src->best.get() : src->plane.get(), sel, flat, st)) return e;
+        put_plane(dst, kd, i == 3 ? dst->best.get() : dst->plane.get(), sel, i == 0 ? PK_SET : PK_PUT, i == 0, flat, st);
     }
     return hipGetLastError();
 }
 
-// the kept-best plane of a population that has none yet: every candidate's starts as a copy of its live parameters
-static int ensure_best(mfas_population* p, hipStream_t st) {
-    if (p->best) return MFAS_OK;
-    HIPCHK(hipMalloc(&p->best, sizeof(float) * (size_t)p->plan.plane_stride));
-    HIPCHK(hipMemcpyAsync(p->best, p->plane, sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, st));
-    return MFAS_OK;
+// The kept-best plane: allocated here and nowhere else, when a caller first needs it.  `init` = what it holds on return:
+//   BEST_LIVE_IF_NEW  a new plane is a copy of the live parameters, an existing one keeps the other candidates' best: set_state of plane 3, the destination of a move
+//   BEST_LIVE         a copy of the live parameters, new or not: train_begin of a schedule that starts with a dev pass (best_model_sd = the INITIAL state_dict)
+//   BEST_AS_IS        a new plane as allocated, an existing one as it is: train_begin otherwise (a later segment goes on; without a dev pass nothing reads it)
+//   BEST_ZERO         a new plane zeroed: persist_fallback's launch-per-phase record, before every candidate's is carried into it
+enum BestInit { BEST_LIVE_IF_NEW, BEST_LIVE, BEST_AS_IS, BEST_ZERO };
+static hipError_t keep_best(mfas_population* p, BestInit init, hipStream_t st) {
+    const size_t n = (size_t)p->plan.plane_stride;
+    const bool fresh = !p->best;
+    if (fresh) if (hipError_t e = p->best.alloc(n)) return e;
+    if (init == BEST_LIVE || (init == BEST_LIVE_IF_NEW && fresh)) return hipMemcpyAsync(p->best.get(), p->plane.get(), sizeof(float) * n, hipMemcpyDeviceToDevice, st);
+    if (init == BEST_ZERO && fresh) return hipMemsetAsync(p->best.get(), 0, sizeof(float) * n, st);
+    return hipSuccess;
 }
 
 // torch.manual_seed(seeds[k]) + the module's construction draws for every candidate, on the device (k_mt_uniform, pack.hip.h).
@@ -109,12 +116,11 @@ extern "C" int mfas_population_init_torch_streams(mfas_population* p, const uint
     int64_t maxp = 0;
     for (int k = 0; k < K; ++k) maxp = std::max(maxp, p->plan.nparams[k]);
     const int batch = (int)std::max<int64_t>(1, std::min<int64_t>(K, (64LL << 20) / std::max<int64_t>(maxp, 1)));     // <= 256 MB of flat scratch
-    float* flat = nullptr; MtCand* d_mt = nullptr; uint32_t* d_tail = nullptr;
-    auto cleanup = [&]() { hipFree(flat); hipFree(d_mt); hipFree(d_tail); };
-    hipError_t e = hipMalloc(&flat, sizeof(float) * (size_t)maxp * batch);
-    if (e == hipSuccess) e = hipMalloc(&d_mt, sizeof(MtCand) * batch);
-    if (e == hipSuccess) e = hipMalloc(&d_tail, sizeof(uint32_t) * MT_TAIL * batch);
-    if (e != hipSuccess) { cleanup(); return fail(MFAS_ENOMEM, std::string("init_torch_streams: ") + hipGetErrorString(e)); }
+    DevBuf<float> flat; DevBuf<MtCand> d_mt; DevBuf<uint32_t> d_tail;      // scratch of this call
+    hipError_t e = flat.alloc((size_t)maxp * batch);
+    if (e == hipSuccess) e = d_mt.alloc(batch);
+    if (e == hipSuccess) e = d_tail.alloc((size_t)MT_TAIL * batch);
+    if (e != hipSuccess) return fail(MFAS_ENOMEM, std::string("init_torch_streams: ") + hipGetErrorString(e));
     std::vector<MtCand> mt(batch);
     std::vector<uint32_t> tails((size_t)MT_TAIL * batch);
     std::vector<float> alpha((size_t)MFAS_MAX_CELLS * batch);
@@ -122,11 +128,11 @@ extern "C" int mfas_population_init_torch_streams(mfas_population* p, const uint
         const int nb = std::min(batch, K - k0);
         for (int j = 0; j < nb; ++j)
             mt_segments(p->plan.cands[k0 + j], R, C, bounds + (size_t)(k0 + j) * NB, (uint32_t)(seeds[k0 + j] & 0xffffffffULL), (int64_t)j * maxp, mt[j]);
-        e = hipMemcpyAsync(d_mt, mt.data(), sizeof(MtCand) * nb, hipMemcpyHostToDevice, p->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(flat, 0, sizeof(float) * (size_t)maxp * nb, p->stream);
+        e = hipMemcpyAsync(d_mt.get(), mt.data(), sizeof(MtCand) * nb, hipMemcpyHostToDevice, p->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(flat.get(), 0, sizeof(float) * (size_t)maxp * nb, p->stream);
         if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_mt_uniform, dim3(nb), dim3(256), 0, p->stream, d_mt, flat, d_tail);
-        e = hipMemcpyAsync(tails.data(), d_tail, sizeof(uint32_t) * MT_TAIL * nb, hipMemcpyDeviceToHost, p->stream);
+        hipLaunchKernelGGL(k_mt_uniform, dim3(nb), dim3(256), 0, p->stream, d_mt.get(), flat.get(), d_tail.get());
+        e = hipMemcpyAsync(tails.data(), d_tail.get(), sizeof(uint32_t) * MT_TAIL * nb, hipMemcpyDeviceToHost, p->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
         if (e != hipSuccess) break;
         for (int j = 0; j < nb && e == hipSuccess; ++j) {
@@ -134,18 +140,17 @@ extern "C" int mfas_population_init_torch_streams(mfas_population* p, const uint
             const CandDev& c = p->plan.cands[k];
             // BatchNorm defaults (gamma = 1, running_var = 1) and the alphas, then the usual repacking of a flat vector
             draw_alphas(tails.data() + (size_t)j * MT_TAIL, c.L, alpha_mean, alpha_std, alpha.data() + (size_t)j * MFAS_MAX_CELLS);
-            float* fk = flat + (int64_t)j * maxp;
+            float* fk = flat.get() + (int64_t)j * maxp;
             e = hipMemcpyAsync(fk + c.f_alpha, alpha.data() + (size_t)j * MFAS_MAX_CELLS, sizeof(float) * c.L, hipMemcpyHostToDevice, p->stream);
             if (e != hipSuccess) break;
             for (int i = 0; i < c.L && p->hp.bn; ++i) {
                 hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, p->stream, fk + c.f_bn[i], 1.0f, (int64_t)R);             // gamma
                 hipLaunchKernelGGL(k_fill, dim3(1), dim3(256), 0, p->stream, fk + c.f_bn[i] + 3 * (int64_t)R, 1.0f, (int64_t)R);   // running_var
             }
-            if (const int rc = mfas_population_set_params(p, k, fk)) { cleanup(); return rc; }
+            if (const int rc = mfas_population_set_params(p, k, fk)) return rc;
         }
         if (e == hipSuccess) e = hipStreamSynchronize(p->stream);       // the scratch is reused by the next batch
     }
-    cleanup();
     if (e != hipSuccess) return fail(MFAS_EHIP, std::string("init_torch_streams: ") + hipGetErrorString(e));
     return MFAS_OK;
 }
@@ -166,17 +171,13 @@ extern "C" int mfas_population_move(mfas_population* dst, int32_t kd, mfas_popul
         return fail(MFAS_EINVAL, "move: candidate " + std::to_string(ks) + " of the source and slot " + std::to_string(kd) + " of the destination have different configurations");
     HIPCHK(hipSetDevice(dst->device));
     const int64_t n = src->plan.nparams[ks];
-    if (dst->move_cap < n) {
-        HIPCHK(hipStreamSynchronize(dst->stream));      // (an earlier move may still read the scratch)
-        hipFree(dst->d_move); dst->d_move = nullptr; dst->move_cap = 0;
-        HIPCHK(hipMalloc(&dst->d_move, sizeof(float) * (size_t)n));
-        dst->move_cap = n;
-    }
+    if (dst->d_move.size() < (size_t)n) HIPCHK(hipStreamSynchronize(dst->stream));      // (an earlier move may still read the scratch)
+    HIPCHK(dst->d_move.reserve((size_t)n));
     const bool with_best = src->best && src->prog.keeps_best[ks];
-    if (with_best) if (int rc = ensure_best(dst, dst->stream)) return rc;
+    if (with_best) HIPCHK(keep_best(dst, BEST_LIVE_IF_NEW, dst->stream));
     if (src->stream != dst->stream) HIPCHK(hipStreamSynchronize(src->stream));      // what src trained is in memory
-    HIPCHK(carry_candidate(dst, kd, src, ks, with_best, dst->d_move, dst->stream));
-    HIPCHK(hipMemcpyAsync(dst->d_status + kd, src->d_status + ks, sizeof(int32_t), hipMemcpyDeviceToDevice, dst->stream));
+    HIPCHK(carry_candidate(dst, kd, src, ks, with_best, dst->d_move.get(), dst->stream));
+    HIPCHK(hipMemcpyAsync(dst->d_status.get() + kd, src->d_status.get() + ks, sizeof(int32_t), hipMemcpyDeviceToDevice, dst->stream));
     dst->prog.done[kd] = src->prog.done[ks]; dst->prog.nb[kd] = src->prog.nb[ks];
     dst->prog.best_metric[kd] = src->prog.best_metric[ks]; dst->prog.keeps_best[kd] = with_best ? 1 : 0;
     return MFAS_OK;
@@ -200,30 +201,25 @@ static int persist_fallback(mfas_population* p) {
             for (int j = 0; j < 3; ++j) confs[(k * 4 + i) * 3 + j] = c.conf[i][j];
         maxp = std::max(maxp, p->plan.nparams[k]);
     }
-    mfas_population* q = nullptr;
-    int rc = create_impl(&p->hp, confs.data(), ncells.data(), seeds.data(), K, p->device, p->stream, p->chunk_cols_req, &q, false, &p->tune);
-    if (rc) return rc;
-    float* flat = nullptr;
-    hipError_t e = hipMalloc(&flat, sizeof(float) * (size_t)maxp);
-    if (e != hipSuccess) { mfas_population_destroy(q); return fail(MFAS_ENOMEM, "persist_fallback: scratch"); }
-    if (p->best && !q->best) {
-        e = hipMalloc(&q->best, sizeof(float) * (size_t)q->plan.plane_stride);
-        if (e == hipSuccess) e = hipMemsetAsync(q->best, 0, sizeof(float) * (size_t)q->plan.plane_stride, p->stream);
-        if (e != hipSuccess) { hipFree(flat); mfas_population_destroy(q); return fail(MFAS_ENOMEM, "persist_fallback: snapshot"); }
-    }
-    for (int k = 0; k < K && e == hipSuccess; ++k) e = carry_candidate(q, k, p, k, p->best != nullptr, flat, p->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(q->d_posw, p->d_posw, sizeof(float) * p->plan.g.Cp, hipMemcpyDeviceToDevice, p->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(q->d_status, p->d_status, sizeof(int32_t) * K, hipMemcpyDeviceToDevice, p->stream);
+    mfas_population* made = nullptr;
+    if (int rc = create_impl(&p->hp, confs.data(), ncells.data(), seeds.data(), K, p->device, p->stream, p->chunk_cols_req, &made, false, &p->tune)) return rc;
+    std::unique_ptr<mfas_population> q(made);      // (leaves with this function: the new record on a failure, the resident layout after the swap)
+    DevBuf<float> flat;
+    if (flat.alloc((size_t)maxp) != hipSuccess) return fail(MFAS_ENOMEM, "persist_fallback: scratch");
+    const bool with_best = (bool)p->best;
+    if (with_best && keep_best(q.get(), BEST_ZERO, p->stream) != hipSuccess) return fail(MFAS_ENOMEM, "persist_fallback: snapshot");
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < K && e == hipSuccess; ++k) e = carry_candidate(q.get(), k, p, k, with_best, flat.get(), p->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(q->d_posw.get(), p->d_posw.get(), sizeof(float) * p->plan.g.Cp, hipMemcpyDeviceToDevice, p->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(q->d_status.get(), p->d_status.get(), sizeof(int32_t) * K, hipMemcpyDeviceToDevice, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    hipFree(flat);
-    if (e != hipSuccess) { mfas_population_destroy(q); return fail(MFAS_EHIP, std::string("persist_fallback: ") + hipGetErrorString(e)); }
-    // the handle keeps the whole progress record, the stats / scalar / event storage and what it was asked to profile
-    std::swap(q->d_stats, p->d_stats); std::swap(q->stats_cap, p->stats_cap);
-    std::swap(q->d_scal, p->d_scal); std::swap(q->scal_cap, p->scal_cap);
-    q->ev.swap(p->ev); q->profiling = p->profiling; q->prof_every = p->prof_every;
+    if (e != hipSuccess) return fail(MFAS_EHIP, std::string("persist_fallback: ") + hipGetErrorString(e));
+    // the handle keeps the whole progress record, the stats / event storage and what it was asked to profile (the device copy of the
+    // step scalars goes with the resident layout: only k_president reads it)
+    std::swap(q->d_stats, p->d_stats);
+    std::swap(q->ev, p->ev); q->profiling = p->profiling; q->prof_every = p->prof_every;
     q->best_threshold = p->best_threshold; q->prog = p->prog; q->fell_back = 1;
     q->launched = p->launched;      // (the call's launch record goes on: the resident launches that were made, then the launch-per-phase ones)
     std::swap(*p, *q);
-    mfas_population_destroy(q);      // the resident layout
     return MFAS_OK;
 }

@@ -29,11 +29,20 @@ struct TrainCall {
 // launch and single_batch share.  What a launch adds: work list, positions, step scalars, flags.
 static void base_args(mfas_population* p, const mfas_table& tab, const int32_t* order, const Geo& g, const AdamC& ac, SweepArgs& sa, ChainArgs& ca) {
     const LayoutPlan& pl = p->plan;
-    sa.cands = p->d_cands; sa.plane = p->plane; sa.plane_stride = pl.plane_stride; sa.wt = p->wt;
-    sa.stepbuf = p->stepbuf; sa.tab = tab; sa.order = order; sa.g = g; sa.ac = ac;
-    ca.plane = p->plane; ca.plane_stride = pl.plane_stride; ca.wt = p->wt; ca.stepbuf = p->stepbuf;
-    ca.tab = tab; ca.order = order; ca.g = g; ca.status = p->d_status; ca.ac = ac;
-    ca.yf_in_lds = pl.yf_in_lds ? 1 : 0; ca.vec_in_lds = pl.vec_in_lds ? 1 : 0; ca.pos_w = p->d_posw;
+    sa.cands = p->d_cands.get(); sa.plane = p->plane.get(); sa.plane_stride = pl.plane_stride; sa.wt = p->wt.get();
+    sa.stepbuf = p->stepbuf.get(); sa.tab = tab; sa.order = order; sa.g = g; sa.ac = ac;
+    ca.plane = p->plane.get(); ca.plane_stride = pl.plane_stride; ca.wt = p->wt.get(); ca.stepbuf = p->stepbuf.get();
+    ca.tab = tab; ca.order = order; ca.g = g; ca.status = p->d_status.get(); ca.ac = ac;
+    ca.yf_in_lds = pl.yf_in_lds ? 1 : 0; ca.vec_in_lds = pl.vec_in_lds ? 1 : 0; ca.pos_w = p->d_posw.get();
+}
+
+// base_args' counterpart for k_eval: the step-independent EvalArgs of population p over one table, reading the parameters at plane_base
+// (p->plane or p->best) — one schedule of one epoch (E = 1).  What a caller adds: rows, candidate, epoch, statistics and output pointers.
+static EvalArgs eval_args(mfas_population* p, const mfas_table& tab, float* plane_base, const Geo& g) {
+    EvalArgs ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.cands = p->d_cands.get(); ea.plane = plane_base; ea.tab = tab; ea.g = g; ea.pos_w = p->d_posw.get(); ea.E = 1;
+    return ea;
 }
 
 static hipError_t setup_gather(TrainCall& c) {
@@ -45,12 +54,7 @@ static hipError_t setup_gather(TrainCall& c) {
     for (int u = 0; u < MFAS_MAX_TAPS; ++u) totw += g.sw[u] + g.vw[u];
     c.g_par_stride = totw * g.Bp * c.elt(); c.g_cand_stride = row_sets(p->plan.defer) * c.g_par_stride;     // (a deferring plan keeps three batches)
     const size_t need = (size_t)c.g_cand_stride * p->K;
-    if (p->gather_cap < need) {
-        hipFree(p->d_gather); p->d_gather = nullptr; p->gather_cap = 0;
-        hipError_t e = hipMalloc(&p->d_gather, need);
-        if (e != hipSuccess) { c.use_gather = false; (void)hipGetLastError(); return hipSuccess; }   // an optimisation: train without it
-        p->gather_cap = need;
-    }
+    if (p->d_gather.reserve(need) != hipSuccess) { c.use_gather = false; (void)hipGetLastError(); return hipSuccess; }   // an optimisation: train without it
     if (p->tune.gather_verbose)
         fprintf(stderr, "[gather] on: %d candidates, %.1f MB of gathered rows, %d row sets%s\n", p->K, (double)need / 1e6, row_sets(p->plan.defer),
                 p->plan.defer ? " (feature segments store W / m / v every second step)" : "");
@@ -66,20 +70,20 @@ static hipError_t init_args(TrainCall& c, int64_t ep) {
     g.order_stride = (p->hp.order_per_candidate && c.order) ? (int64_t)c.epochs * c.N : 0;    // order: [K][epochs][N_train]
     memset(&st, 0, sizeof(st));
     base_args(p, *c.train, c.order, g, c.ac, st.sa, st.ca);
-    st.ca.E = c.epochs; st.ca.stats = p->d_stats;
-    st.sa.red_cnt = pl.red_in_sweep ? p->d_red_cnt : nullptr; st.ca.yf_reduced = pl.red_in_sweep ? 1 : 0;
+    st.ca.E = c.epochs; st.ca.stats = p->d_stats.get();
+    st.sa.red_cnt = p->d_red_cnt.get(); st.ca.yf_reduced = pl.red_in_sweep ? 1 : 0;
     hipError_t e_ = hipSuccess;
-    if (pl.red_in_sweep) e_ = hipMemsetAsync(p->d_red_cnt, 0, sizeof(uint32_t) * K * MFAS_MAX_CELLS, p->stream);
-    if (e_ == hipSuccess && pl.same_group) e_ = hipMemsetAsync(p->d_cellflag, 0, sizeof(uint32_t) * K * CELLFLAG_STRIDE, p->stream);
+    if (pl.red_in_sweep) e_ = hipMemsetAsync(p->d_red_cnt.get(), 0, sizeof(uint32_t) * K * MFAS_MAX_CELLS, p->stream);
+    if (e_ == hipSuccess && pl.same_group) e_ = hipMemsetAsync(p->d_cellflag.get(), 0, sizeof(uint32_t) * K * CELLFLAG_STRIDE, p->stream);
     // chain_split: every piece of both parities "not written" (all-ones words), parity counter back to 0
-    if (e_ == hipSuccess && pl.chain_split) e_ = hipMemsetAsync(p->d_xch, 0xFF, sizeof(float) * (size_t)K * XCH_CAND_FLOATS, p->stream);
-    st.ca.xch = p->d_xch; st.ca.nsplit = pl.chain_split; st.ca.xpar = 0;
+    if (e_ == hipSuccess && pl.chain_split) e_ = hipMemsetAsync(p->d_xch.get(), 0xFF, sizeof(float) * (size_t)K * XCH_CAND_FLOATS, p->stream);
+    st.ca.xch = p->d_xch.get(); st.ca.nsplit = pl.chain_split; st.ca.xpar = 0;
     c.split_launches[0] = c.split_launches[1] = 0;
     // chain_split in the same-group launch counts ARRIVALS on the per-cell flags: every part adds 1 per step and a sweep unit waits for
     // parts * (gstep + 1).  Zero is right for a call that starts at step 0; one that starts at epoch ep (a later segment, or a fallback
     // mid-call) starts them where steps 0 .. ep * nb - 1 would have left them.  (The one-part chain stores its target and needs nothing.)
     if (e_ == hipSuccess && ep > 0 && pl.same_group && pl.chain_split)
-        e_ = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->d_cellflag), (int)((uint32_t)pl.chain_split * (uint32_t)(ep * c.nb)),
+        e_ = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p->d_cellflag.get()), (int)((uint32_t)pl.chain_split * (uint32_t)(ep * c.nb)),
                                (size_t)K * CELLFLAG_STRIDE, p->stream);
     return e_ != hipSuccess ? e_ : setup_gather(c);
 }
@@ -87,20 +91,20 @@ static hipError_t init_args(TrainCall& c, int64_t ep) {
 // HIP events around one profiled launch (the pairs are kept in the population and reused by later calls)
 struct ProfBracket {
     TrainCall& c;
-    const bool on;
+    bool on;                        // (off for this launch when its events cannot be created)
     const double bytes;             // algorithmic HBM bytes of the launch
     ProfBracket(TrainCall& c_, bool on_, double bytes_) : c(c_), on(on_), bytes(bytes_) {
         if (!on) return;
         mfas_population* p = c.p;
-        if (p->ev.size() < c.ev_used + 2) {
-            hipEvent_t e0, e1;
-            hipEventCreate(&e0); hipEventCreate(&e1); p->ev.push_back(e0); p->ev.push_back(e1);
+        if (p->ev.v.size() < c.ev_used + 2 && !p->ev.add_pair()) {
+            on = false;
+            return;
         }
-        hipEventRecord(p->ev[c.ev_used], p->stream);
+        hipEventRecord(p->ev.v[c.ev_used], p->stream);
     }
     ~ProfBracket() {
         if (!on) return;
-        hipEventRecord(c.p->ev[c.ev_used + 1], c.p->stream);
+        hipEventRecord(c.p->ev.v[c.ev_used + 1], c.p->stream);
         c.ev_used += 2; c.ev_bytes.push_back(bytes);
     }
 };
@@ -118,14 +122,14 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
     st.ga.nblocks = 0; st.ga.nsets = 0; st.sa.gather = nullptr;
     if (c.use_gather) {
         GatherArgs& ga = st.ga;
-        ga.buf = p->d_gather; ga.cand_stride = c.g_cand_stride; ga.par_stride = c.g_par_stride;
+        ga.buf = p->d_gather.get(); ga.cand_stride = c.g_cand_stride; ga.par_stride = c.g_par_stride;
         for (int s = 0; s < L.gather_n; ++s) {
             const int64_t t = L.gather_b + s;
             ga.pos[s] = ep * N + t * B; ga.base[s] = (int)(t * B); ga.nvalid[s] = nvalid(t); ga.par[s] = row_set_of(t, pl.defer);
         }
-        if (L.gather_g >= 0) { ga.nsets = L.gather_n; ga.cands = p->d_cands + pl.groups[L.gather_g].c0; ga.nblocks = pl.groups[L.gather_g].nc; }
+        if (L.gather_g >= 0) { ga.nsets = L.gather_n; ga.cands = p->d_cands.get() + pl.groups[L.gather_g].c0; ga.nblocks = pl.groups[L.gather_g].nc; }
         if (gs >= 0 && L.upd) {
-            st.sa.gather = p->d_gather; st.sa.g_cand_stride = c.g_cand_stride; st.sa.g_par_stride = c.g_par_stride;
+            st.sa.gather = p->d_gather.get(); st.sa.g_cand_stride = c.g_cand_stride; st.sa.g_par_stride = c.g_par_stride;
             st.sa.g_par_t = row_set_of(L.sweep_t, pl.defer); st.sa.g_par_n = row_set_of(L.sweep_t + 1, pl.defer);
             st.sa.g_par_p = row_set_of(std::max<int64_t>(L.sweep_t - 1, 0), pl.defer);
         }
@@ -133,8 +137,8 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
     if (gs >= 0) {
         SweepArgs& s = st.sa;
         const int64_t ts = L.sweep_t, tn = L.fwd && L.upd ? ts + 1 : ts, gstep = ep * c.nb + ts;
-        s.desc = p->groups[gs].d_descs;
-        s.tdesc = p->groups[gs].d_taps; s.ntap = (int)pl.groups[gs].taps.size();
+        s.desc = p->groups[gs].d_descs.get();
+        s.tdesc = p->groups[gs].d_taps.get(); s.ntap = (int)pl.groups[gs].taps.size();
         s.do_update = L.upd; s.do_forward = L.fwd;
         s.pos_t = ep * N + ts * B; s.base_t = (int)(ts * B); s.nvalid_t = nvalid(ts);
         s.pos_n = ep * N + tn * B; s.base_n = (int)(tn * B); s.nvalid_n = nvalid(tn);
@@ -153,7 +157,7 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
     if (gc >= 0) {
         ChainArgs& ca = st.ca;
         const int64_t tc = L.chain_t, gstep = ep * c.nb + tc;
-        ca.cands = p->d_cands + pl.groups[gc].c0;
+        ca.cands = p->d_cands.get() + pl.groups[gc].c0;
         ca.pos_t = ep * N + tc * B; ca.base_t = (int)(tc * B); ca.nvalid = nvalid(tc);
         ca.gstep = (int)gstep; ca.epoch = (int)ep;
         ca.ac.ss = c.step_scalars[2 * gstep]; ca.ac.bc2s = c.step_scalars[2 * gstep + 1];
@@ -181,9 +185,9 @@ static void launch_record(TrainCall& c, int64_t ep, const Launch& L) {
         st.nchain = pl.chain_split * (int)((nch + 7) & ~7u);
     }
     if (same) {       // (NS parts: the per-cell flags count arrivals)
-        st.sa.cellflag = p->d_cellflag; st.ca.cellflag = p->d_cellflag;
+        st.sa.cellflag = st.ca.cellflag = p->d_cellflag.get();
         st.sa.flag_target = st.ca.flag_target = (split ? (uint32_t)pl.chain_split : 1u) * ((uint32_t)st.ca.gstep + 1u);
-        st.sa.flag_status = p->d_status;
+        st.sa.flag_status = p->d_status.get();
     }
     const BuildKey key = step_key(plan_facts(pl), nch, same, pl.groups[gs].alg_state > pl.occ_bytes);
     launch_build(p, step_build(key), (unsigned)st.nchain + st.ga.nblocks + nsw, split ? pl.lds_split : pl.lds_step, p->stream, st);
@@ -198,20 +202,20 @@ static hipError_t persist_epoch_once(TrainCall& c, int ep, int64_t T) {
     const int K = p->K;
     // (test_not_resident: -1 in the product library; the MFAS_TEST_HOOKS variant: from this epoch on every roll call "fails" — nothing is launched)
     if (p->tune.test_not_resident >= 0 && ep >= p->tune.test_not_resident) { c.aborts[ep] = PERSIST_ABORT_NOT_RESIDENT; return hipSuccess; }
-    hipError_t e = hipMemsetAsync(p->d_sync, 0, sizeof(uint32_t) * ((size_t)K * PERSIST_SYNC_STRIDE + 64), p->stream);
+    hipError_t e = hipMemsetAsync(p->d_sync.get(), 0, sizeof(uint32_t) * ((size_t)K * PERSIST_SYNC_STRIDE + 64), p->stream);
     if (e != hipSuccess) return e;
     PersistArgs pa;
     memset(&pa, 0, sizeof(pa));
     pa.sa = c.st.sa; pa.ca = c.st.ca;      // (init_args: the step-independent arguments)
-    pa.sa.desc = p->d_pdescs; pa.sa.tdesc = nullptr; pa.sa.ntap = 0;
-    pa.ca.cands = p->d_cands;
+    pa.sa.desc = p->d_pdescs.get(); pa.sa.tdesc = nullptr; pa.sa.ntap = 0;
+    pa.ca.cands = p->d_cands.get();
     pa.nchain = K; pa.nitems = (int)pl.pdescs.size(); pa.nres = pl.nres; pa.res_chain = pl.res_chain ? 1 : 0; pa.res_wide = pl.res_wide ? 1 : 0;
     pa.res_nu = pl.res_nu; pa.nres_wg = pl.nres_wg; pa.res_buf_words = pl.res_buf_words;
     pa.T = (int)T; pa.epoch = ep;
     pa.lose_step = p->tune.test_lose_step;
     pa.N = c.N; pa.pos0 = (int64_t)ep * c.N;
     pa.B = c.B; pa.gstep0 = (int)((int64_t)ep * c.nb);
-    pa.scal = p->d_scal; pa.sync = p->d_sync; pa.need = p->d_need; pa.role = p->d_role; pa.trace = p->d_trace;
+    pa.scal = p->d_scal.get(); pa.sync = p->d_sync.get(); pa.need = p->d_need.get(); pa.role = p->d_role.get(); pa.trace = p->d_trace.get();
     const unsigned grid = (unsigned)(K + pa.nres_wg);
     if ((int)grid > p->n_cus) return hipErrorInvalidConfiguration;
     {
@@ -224,7 +228,7 @@ static hipError_t persist_epoch_once(TrainCall& c, int ep, int64_t T) {
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return hipMemcpyAsync(&c.aborts[ep], p->d_sync + (size_t)K * PERSIST_SYNC_STRIDE, sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream);
+    return hipMemcpyAsync(&c.aborts[ep], p->d_sync.get() + (size_t)K * PERSIST_SYNC_STRIDE, sizeof(uint32_t), hipMemcpyDeviceToHost, p->stream);
 }
 
 // The launch is only valid when its whole grid is resident at once (roll call, persist.hip.h).  When another process holds
@@ -252,7 +256,7 @@ static hipError_t persist_epoch(TrainCall& c, int ep, int64_t T) {
 // MFAS_PERSIST_TRACE: the step-phase timestamps of the last resident launch
 static void dump_persist_trace(const mfas_population* p) {
     unsigned long long tr[256];
-    if (hipMemcpy(tr, p->d_trace, sizeof(tr), hipMemcpyDeviceToHost) != hipSuccess) return;
+    if (hipMemcpy(tr, p->d_trace.get(), sizeof(tr), hipMemcpyDeviceToHost) != hipSuccess) return;
     // step 12 of candidate 0: chain published at tr[4*8+3]; per resident unit: saw-flag / compute-done / arrived, relative to it
     const long long pub = (long long)tr[4 * 8 + 3];
     fprintf(stderr, "[persist trace step 12, candidate 0 units, ticks after the chain published: saw-flag done arrived]");
@@ -270,7 +274,7 @@ static void dump_persist_trace(const mfas_population* p) {
 #ifdef MFAS_CHAIN_TIMING
 static void dump_chain_timing(const mfas_population* p) {
     int32_t ts[40];
-    if (hipMemcpy(ts, p->d_status + 64, sizeof(ts), hipMemcpyDeviceToHost) != hipSuccess) return;
+    if (hipMemcpy(ts, p->d_status.get() + 64, sizeof(ts), hipMemcpyDeviceToHost) != hipSuccess) return;
     fprintf(stderr, "[chain timing, shader cycles since kernel entry, candidate 0 step 3]");
     for (int i = 0; i < 13; ++i) fprintf(stderr, " %d", ts[i]);
     if (p->plan.chain_split) {      // chain_split's extra stamps: forward cell 1 product done | out sent | tail done | fetched;  backward cell 2 the same;  softmax done;  entry staged
@@ -282,14 +286,14 @@ static void dump_chain_timing(const mfas_population* p) {
         fprintf(stderr, "; unit (cell 0, S, chunk 0) after the end of chain 3: flag seen %d, dy staged %d, tiles done %d, slab drained %d, arrival counted %d",
                 ts[29] - ts[24], ts[30] - ts[24], ts[31] - ts[24], ts[32] - ts[24], ts[33] - ts[24]);
         int32_t ue[16];
-        if (hipMemcpy(ue, p->d_status + 128, sizeof(ue), hipMemcpyDeviceToHost) == hipSuccess) {
+        if (hipMemcpy(ue, p->d_status.get() + 128, sizeof(ue), hipMemcpyDeviceToHost) == hipSuccess) {
             fprintf(stderr, "; last unit end after the end of chain 3, per cell [S V OUT HEAD]:");
             for (int i = 0; i < 16; ++i) fprintf(stderr, "%s%d", (i & 3) ? " " : " | ", ue[i] ? (int32_t)((uint32_t)ue[i] - (uint32_t)ts[24]) : 0);
         }
     }
     fprintf(stderr, "\n");
     int32_t cs[24];
-    if (hipMemcpy(cs, p->d_status + 96, sizeof(cs), hipMemcpyDeviceToHost) == hipSuccess) {
+    if (hipMemcpy(cs, p->d_status.get() + 96, sizeof(cs), hipMemcpyDeviceToHost) == hipSuccess) {
         fprintf(stderr, "[chain checksums, candidate 0 global step 0: sums x4, out x4, logits, dlogits, dy x4, d x4]");
         for (int i = 0; i < 18; ++i) fprintf(stderr, " %08x", (unsigned)cs[i]);
         fprintf(stderr, "\n");
@@ -338,25 +342,20 @@ static int train_begin(TrainCall& c) {
     const int K = p->K, epochs = c.epochs;
     const size_t plane = (size_t)p->plan.plane_stride;
     if (!c.segment) p->prog.reset(K, p->best_threshold);      // a plain train() call owes nothing to an earlier schedule
-    if (p->stats_cap < K * epochs) {
-        hipFree(p->d_stats); p->d_stats = nullptr;
-        HIPCHK(hipMalloc(&p->d_stats, sizeof(DevStats) * K * epochs));
-        p->stats_cap = K * epochs;
-    }
-    HIPCHK(hipMemsetAsync(p->d_stats, 0, sizeof(DevStats) * K * epochs, p->stream));
-    if (!c.resume) HIPCHK(hipMemsetAsync(p->d_status, 0, sizeof(int32_t) * K, p->stream));      // (sticky across the segments of a schedule)
+    HIPCHK(p->d_stats.reserve((size_t)K * epochs));
+    HIPCHK(hipMemsetAsync(p->d_stats.get(), 0, sizeof(DevStats) * K * epochs, p->stream));
+    if (!c.resume) HIPCHK(hipMemsetAsync(p->d_status.get(), 0, sizeof(int32_t) * K, p->stream));      // (sticky across the segments of a schedule)
 #ifdef MFAS_CHAIN_TIMING
-    HIPCHK(hipMemsetAsync(p->d_status + 64 + 27, 0, sizeof(int32_t), p->stream));
-    HIPCHK(hipMemsetAsync(p->d_status + 128, 0, 16 * sizeof(int32_t), p->stream));
-    HIPCHK(hipMemsetAsync(p->d_status + 64 + 28, 0xFF, sizeof(int32_t), p->stream));
+    HIPCHK(hipMemsetAsync(p->d_status.get() + 64 + 27, 0, sizeof(int32_t), p->stream));
+    HIPCHK(hipMemsetAsync(p->d_status.get() + 128, 0, 16 * sizeof(int32_t), p->stream));
+    HIPCHK(hipMemsetAsync(p->d_status.get() + 64 + 28, 0xFF, sizeof(int32_t), p->stream));
 #endif
     // every call is a freshly built torch.optim.Adam (ntu_searchable.py:65; main_found_ntu.py:108,128): zero exp_avg / exp_avg_sq
     // (a segment that goes on finds the optimizer's state where the previous one left it)
-    if (!c.resume) HIPCHK(hipMemsetAsync(p->plane + plane, 0, sizeof(float) * 2 * plane, p->stream));
-    if (c.snapshot_best && !p->best) HIPCHK(hipMalloc(&p->best, sizeof(float) * plane));
+    if (!c.resume) HIPCHK(hipMemsetAsync(p->plane.get() + plane, 0, sizeof(float) * 2 * plane, p->stream));
     // best_model_sd starts as a copy of the INITIAL state_dict (train_searchable/ntu.py:17) and is what the model is
     // left with if no epoch's dev metric beats the starting threshold (0 for accuracy, init_f1 for F1)
-    if (c.snapshot_best && c.do_dev && !c.resume) HIPCHK(hipMemcpyAsync(p->best, p->plane, sizeof(float) * plane, hipMemcpyDeviceToDevice, p->stream));
+    if (c.snapshot_best) HIPCHK(keep_best(p, c.do_dev && !c.resume ? BEST_LIVE : BEST_AS_IS, p->stream));
     c.best_acc.assign(K, p->best_threshold);
     if (c.resume) c.best_acc = p->prog.best_metric;
     c.metric_scale = p->plan.g.loss_mode == 1 ? 1.0 / 4294967296.0 : 1.0;   // F1 sums are 32.32 fixed point
@@ -369,13 +368,9 @@ static int train_begin(TrainCall& c) {
     p->prof_launches = 0; p->prof_ms = 0.0; p->prof_bytes = 0.0;
     if (p->plan.persist) {   // the step scalars live on the device: the kernel walks the steps itself
         const int64_t steps = (int64_t)epochs * c.nb;
-        if (p->scal_cap < (size_t)steps * 2) {
-            hipFree(p->d_scal); p->d_scal = nullptr;
-            HIPCHK(hipMalloc(&p->d_scal, sizeof(float) * steps * 2));
-            p->scal_cap = (size_t)steps * 2;
-        }
+        HIPCHK(p->d_scal.reserve((size_t)steps * 2));
         const size_t have = (size_t)(c.max_steps >= 0 ? std::min<int64_t>(c.max_steps, steps) : steps) * 2;
-        HIPCHK(hipMemcpyAsync(p->d_scal, c.step_scalars, sizeof(float) * have, hipMemcpyHostToDevice, p->stream));
+        HIPCHK(hipMemcpyAsync(p->d_scal.get(), c.step_scalars, sizeof(float) * have, hipMemcpyHostToDevice, p->stream));
     }
     return MFAS_OK;
 }
@@ -414,19 +409,17 @@ static int train_epoch(TrainCall& c, int ep, int64_t T) {
 static int train_dev(TrainCall& c, int ep) {
     mfas_population* p = c.p;
     const int K = p->K;
-    EvalArgs ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.cands = p->d_cands; ea.plane = p->plane; ea.tab = *c.dev; ea.row0 = 0; ea.nrows = c.dev->N;
-    ea.cand0 = 0; ea.epoch = ep; ea.E = c.epochs; ea.g = c.st.sa.g; ea.stats = p->d_stats; ea.pos_w = p->d_posw;
+    EvalArgs ea = eval_args(p, *c.dev, p->plane.get(), c.st.sa.g);      // (the call's g: its order stride)
+    ea.nrows = c.dev->N; ea.epoch = ep; ea.E = c.epochs; ea.stats = p->d_stats.get();
     HIPCHK(launch_eval(p, ea, K, p->stream));
     if (!c.snapshot_best) return MFAS_OK;
-    HIPCHK(hipMemcpyAsync(c.hstats.data(), p->d_stats, sizeof(DevStats) * K * c.epochs, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(c.hstats.data(), p->d_stats.get(), sizeof(DevStats) * K * c.epochs, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     for (int k = 0; k < K; ++k) {
         const double acc = c.dev_metric(k, ep);
         if (acc > c.best_acc[k]) {   // strict >, from 0 (train_searchable/ntu.py:82) / init_f1 (mmimdb.py:18)
             c.best_acc[k] = acc;
-            HIPCHK(hipMemcpyAsync(p->best + p->plan.cand_plane_base[k], p->plane + p->plan.cand_plane_base[k],
+            HIPCHK(hipMemcpyAsync(p->best.get() + p->plan.cand_plane_base[k], p->plane.get() + p->plan.cand_plane_base[k],
                                   sizeof(float) * p->plan.cand_plane_size[k], hipMemcpyDeviceToDevice, p->stream));
         }
     }
@@ -438,14 +431,14 @@ static int train_end(TrainCall& c, mfas_epoch_stats* stats, int32_t* status) {
     mfas_population* p = c.p;
     const int K = p->K, epochs = c.epochs;
     if (c.snapshot_best && c.do_dev && c.last == epochs) {   // model.load_state_dict(best_model_sd) (:86), unconditionally — once the schedule is complete
-        HIPCHK(hipMemcpyAsync(p->plane, p->best, sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, p->stream));
+        HIPCHK(hipMemcpyAsync(p->plane.get(), p->best.get(), sizeof(float) * (size_t)p->plan.plane_stride, hipMemcpyDeviceToDevice, p->stream));
         // the transposed OUT / HEAD tiles the backward chain reads still hold the last epoch's weights: re-derive them
         run_pack(p, pack_args(p, PK_WT, 0, nullptr), -1, false, p->stream);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipMemcpyAsync(c.hstats.data(), p->d_stats, sizeof(DevStats) * K * epochs, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(c.hstats.data(), p->d_stats.get(), sizeof(DevStats) * K * epochs, hipMemcpyDeviceToHost, p->stream));
     std::vector<int32_t> hstatus(K, 0);
-    HIPCHK(hipMemcpyAsync(hstatus.data(), p->d_status, sizeof(int32_t) * K, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(hstatus.data(), p->d_status.get(), sizeof(int32_t) * K, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     HIPCHK(hipGetLastError());
     for (uint32_t ab : c.aborts)
@@ -472,7 +465,7 @@ static int train_end(TrainCall& c, mfas_epoch_stats* stats, int32_t* status) {
     if (p->profiling) {
         for (size_t i = 0; i + 1 < c.ev_used; i += 2) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, p->ev[i], p->ev[i + 1]) == hipSuccess) { p->prof_ms += ms; p->prof_launches++; p->prof_bytes += c.ev_bytes[i / 2]; }
+            if (hipEventElapsedTime(&ms, p->ev.v[i], p->ev.v[i + 1]) == hipSuccess) { p->prof_ms += ms; p->prof_launches++; p->prof_bytes += c.ev_bytes[i / 2]; }
         }
         p->bytes_per_launch = p->prof_launches ? p->prof_bytes / p->prof_launches : 0.0;
     }
@@ -522,11 +515,11 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
     memset(&st, 0, sizeof(st)); memset(&ca, 0, sizeof(ca));
     base_args(p, *tab, nullptr, g, ac, st.sa, ca);
     // the sweep over this candidate's units alone, forward half first; the chain of this candidate alone, dropout stream of step_index
-    st.sa.desc = pl.wide ? p->groups[0].d_descs + pl.wide_start[k] : p->d_descs + pl.desc_start[k];
+    st.sa.desc = pl.wide ? p->groups[0].d_descs.get() + pl.wide_start[k] : p->d_descs.get() + pl.desc_start[k];
     st.sa.do_update = 0; st.sa.do_forward = 1;
     st.sa.pos_n = st.sa.pos_t = ca.pos_t = row0; st.sa.base_n = st.sa.base_t = ca.base_t = (int)row0;
     st.sa.nvalid_n = st.sa.nvalid_t = ca.nvalid = nrows;
-    ca.cands = p->d_cands + k; ca.gstep = step_index; ca.E = 1;
+    ca.cands = p->d_cands.get() + k; ca.gstep = step_index; ca.E = 1;
     ca.logits_out = dlogits ? nullptr : logits; ca.dlogits_in = dlogits;
     const unsigned nsw = pl.wide ? (unsigned)(pl.wide_start[k + 1] - pl.wide_start[k]) : (unsigned)(pl.desc_start[k + 1] - pl.desc_start[k]);
     size_t lds_need = pl.lds_step;   // (a population laid out for resident units budgets its streaming LDS without them)
@@ -541,7 +534,7 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
         // and a stale second moment would turn the zero-step's 0 * (m / denom) into 0 * inf.  Whatever this handle has trained
         // before, candidate k's m and v planes start from zero here (the header documents them as scratch after this call).
         for (int sel = 1; sel <= 2; ++sel)
-            HIPCHK(hipMemsetAsync(p->plane + sel * pl.plane_stride + pl.cand_plane_base[k], 0, sizeof(float) * (size_t)pl.cand_plane_size[k], p->stream));
+            HIPCHK(hipMemsetAsync(p->plane.get() + sel * pl.plane_stride + pl.cand_plane_base[k], 0, sizeof(float) * (size_t)pl.cand_plane_size[k], p->stream));
     }
     // 1. forward partial sums of the batch (no update): the sweep's forward half over this candidate's units
     sweep();

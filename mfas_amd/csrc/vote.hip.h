@@ -264,33 +264,27 @@ static int evaluate_impl(mfas_population* p, const mfas_table* tab, int32_t plan
                  o_rl = o_out + vote_align(sizeof(VoteOut)), o_lg = o_rl + vote_align(sizeof(float) * (size_t)N),
                  o_sc = o_lg + vote_align((size_t)brows * (size_t)row_bytes),
                  need = o_sc + ((report && !scores) ? vote_align(sizeof(float) * (size_t)N * (size_t)g.C) : 0);
-    if (p->vote_cap < need) {
-        HIPCHK(hipFree(p->d_vote));
-        p->d_vote = nullptr; p->vote_cap = 0;
-        hipError_t e = hipMalloc(&p->d_vote, need);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MFAS_ENOMEM : MFAS_EHIP, std::string("evaluate: arena: ") + hipGetErrorString(e));
-        p->vote_cap = need;
-    }
-    float* d_w = reinterpret_cast<float*>(p->d_vote + o_w);
-    DevStats* d_st = reinterpret_cast<DevStats*>(p->d_vote + o_st);
-    VoteOut* d_out = reinterpret_cast<VoteOut*>(p->d_vote + o_out);
-    float* d_rl = reinterpret_cast<float*>(p->d_vote + o_rl);
-    float* d_lg = reinterpret_cast<float*>(p->d_vote + o_lg);
+    if (hipError_t e = p->d_vote.reserve(need))
+        return fail(e == hipErrorOutOfMemory ? MFAS_ENOMEM : MFAS_EHIP, std::string("evaluate: arena: ") + hipGetErrorString(e));
+    char* const arena = p->d_vote.get();
+    float* d_w = reinterpret_cast<float*>(arena + o_w);
+    DevStats* d_st = reinterpret_cast<DevStats*>(arena + o_st);
+    VoteOut* d_out = reinterpret_cast<VoteOut*>(arena + o_out);
+    float* d_rl = reinterpret_cast<float*>(arena + o_rl);
+    float* d_lg = reinterpret_cast<float*>(arena + o_lg);
     HIPCHK(hipMemcpyAsync(d_w, wn.data(), sizeof(float) * M, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(p->d_vote + o_st, 0, o_rl - o_st, st));
+    HIPCHK(hipMemsetAsync(arena + o_st, 0, o_rl - o_st, st));
     const size_t slots = (size_t)M + 1, nc = (size_t)g.C;
     if (confusion) HIPCHK(hipMemsetAsync(confusion, 0, sizeof(int64_t) * slots * nc * nc, st));
     if (rank_hist) HIPCHK(hipMemsetAsync(rank_hist, 0, sizeof(int64_t) * slots * nc, st));
     if (label_counts) HIPCHK(hipMemsetAsync(label_counts, 0, sizeof(int64_t) * slots * nc * 3, st));
 
-    EvalArgs ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.cands = p->d_cands; ea.plane = plane == 3 ? p->best : p->plane; ea.tab = *tab; ea.E = 1; ea.g = g; ea.pos_w = p->d_posw;
+    EvalArgs ea = eval_args(p, *tab, plane == 3 ? p->best.get() : p->plane.get(), g);
     VoteArgs va;
     memset(&va, 0, sizeof(va));
     va.logits = d_lg; va.weights = d_w; va.label = tab->label; va.vlogit = tab->vlogit; va.slogit = tab->slogit; va.multilabel = tab->multilabel;
-    va.pos_w = p->d_posw; va.N = N; va.M = M; va.C = g.C; va.loss_mode = g.loss_mode; va.multitask = g.multitask; va.combine = combine;
-    va.f1_th = g.f1_th; va.member_preds = member_preds; va.scores = (report && !scores) ? reinterpret_cast<float*>(p->d_vote + o_sc) : scores; va.row_loss = d_rl; va.corr = &d_out->corr;
+    va.pos_w = p->d_posw.get(); va.N = N; va.M = M; va.C = g.C; va.loss_mode = g.loss_mode; va.multitask = g.multitask; va.combine = combine;
+    va.f1_th = g.f1_th; va.member_preds = member_preds; va.scores = (report && !scores) ? reinterpret_cast<float*>(arena + o_sc) : scores; va.row_loss = d_rl; va.corr = &d_out->corr;
     for (int64_t row0 = 0; row0 < N; row0 += brows) {
         const int64_t rows = std::min(brows, N - row0);
         for (int m = 0; m < M; ++m) {

@@ -2,6 +2,7 @@
 the W, m and v planes of every candidate, the per-epoch statistics and the status words must be the same BYTES.
 usage: lib_ab.py LIB_A LIB_B                       bytes A/B over every case below; exit status 1 on a difference
        lib_ab.py LIB_A LIB_B --time CASE [ROUNDS]  ms per train() of one case, the libraries alternating (A B A B ...), one process each
+                                                   (CASE search_call: ms per create + init + train + destroy of a small resident population)
 The cases are the smallest that reach each statement of the general chain (chain_body at 1 / 2 / 4 batch blocks: launch per phase,
 fused, same-group), of chain_split (K = 1, K = 3, the two-group launch) and of the wide path, with every head (<= 64 classes, more,
 multitask, multi-label), BatchNorm on / off, alphas and dropout: the case and schedule tables of tests/test_gpu_ref64.py,
@@ -50,6 +51,39 @@ ENVELOPE_CASES = ("r17a", "r32a", "r33a", "r65b", "r80a", "r128a", "r128b")
 WIDE = ("wb65", "wb128", "w177", "w256", "w80", "wc")
 
 
+def run_search_call(dev, reps):
+    """--time search_call: what one round of the search pays per population — create, init, train, destroy of a small resident
+    population (R = 16, 6 candidates of 1..4 cells, 16-bit tables, 2 epochs of 20 batches, dev pass, kept best) — timed as ONE call, so
+    that allocation and release are inside the measurement.  -> like run_case"""
+    import numpy as np
+    import torch
+    from mfas_amd import FeatureTable, Hyper, Population
+    from oracle import np_oracle as O
+    from tests.helpers import CONFS
+    hp = Hyper(R=16, C=60, B=20, bn=False, drpt=0.5, tap_bits=16)
+    confs = [np.array(CONFS[c]) for c in ("c4", "c0", "l1", "l2", "l3", "c4")]
+    tr, dv = FeatureTable.synthetic(400, 1, dev, torch.bfloat16, snr=0.5), FeatureTable.synthetic(200, 2, dev, torch.bfloat16, snr=0.5)
+    etas = O.eta_sequence(1e-3, 1e-6, 1, 2, 400 / 20, 2 * 20)
+    h, best, sched, ok = hashlib.sha256(), None, None, True
+    for rep in range(max(1, reps)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pop = Population(hp, confs, dev, drop_seeds=list(range(1, 7)))
+        pop.init(list(range(11, 17)))
+        stats, status = pop.train(tr, dv, 2, etas, snapshot_best=True)
+        if rep == 0:
+            sched = pop.schedule()
+            assert sched["persistent"], sched
+        pop.close()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+        if rep == 0:
+            h.update(np.ascontiguousarray(stats).tobytes())
+            ok = not np.asarray(status).any()
+    return h.hexdigest(), {k: sched[k] for k in ("wide", "lean_chain", "chain_cus", "groups", "persistent")}, best, ok
+
+
 def run_case(name, dev, reps):
     """-> (sha256 over planes / statistics / status, schedule, best seconds of a train() call)"""
     import numpy as np
@@ -57,6 +91,8 @@ def run_case(name, dev, reps):
     from tests import gpu_support as G
     from tests import train_gpu as GT
     from tests import wide_gpu as GW
+    if name == "search_call":
+        return run_search_call(dev, reps)
     if name in SCHED_CASES:
         base, entry, edits = SCHED_CASES[name]
         entry = entry or GT.TRAIN_SCHEDULES[base]
