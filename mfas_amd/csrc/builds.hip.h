@@ -1,4 +1,5 @@
-// builds.hip.h — which kernel build a launch takes, as data (host only; plain C++17: no HIP include, no engine type).
+// builds.hip.h — which kernel build a launch takes, as data (host only; plain C++17: no HIP include, no engine type but the shared
+// sizes of records.hip.h).
 // A build is named by a BuildKey: the kernel family and the template arguments of the instantiation.  The choice functions below turn
 // the few plan facts a choice reads (PlanFacts, filled from the LayoutPlan by plan_facts in plan.hip.h) and the launch's own inputs
 // into a key; the kernel tables of mfas_hip.hip turn a key into the function pointer.  plan_keys lists every key a population with
@@ -8,6 +9,7 @@
 #pragma once
 #include <string>
 #include <vector>
+#include "records.hip.h"
 
 enum BuildFamily { F_STEP, F_STEP_SAME, F_SWEEP_WIDE, F_CHAIN, F_CHAIN_WIDE, F_PRESIDENT, F_EVAL, F_NONE };
 
@@ -40,9 +42,6 @@ struct PlanFacts {
     int res_nu = 1;                     // resident units per workgroup
     int mbe = 4, nrbw = 1, nrb = 1;     // dev pass: batch tiles per workgroup, row blocks per wave; the geometry's row blocks
 };
-
-static const int BUILDS_NTR = 4, BUILDS_NTR16 = 8;      // PERSIST_NTR, PERSIST_NTR16 (persist.hip.h; mfas_hip.hip asserts the equality)
-static const int BUILDS_DT_BF16 = 1;                     // MFAS_DT_BF16 (the same)
 
 inline BuildKey step_key_of(int MB, bool nt, int wpe, bool lean, int ns) { return {F_STEP, 5, {MB, nt, wpe, lean, ns}}; }
 inline BuildKey same_key_of(int MB, bool nt, int ns) { return {F_STEP_SAME, 3, {MB, nt, ns, 0, 0}}; }
@@ -80,15 +79,15 @@ inline int president_plain(bool alphas, bool multitask, int loss_mode, bool bn, 
 // one build per unit form: f32 staging (one or two units per workgroup), 16-bit staging (the same, or one WIDE unit of up to 1024
 // columns).  x16: the train table is not f32
 inline BuildKey president_key(const PlanFacts& f, bool x16, int plain) {
-    if (x16 && f.res_wide) return president_key_of(f.MB, BUILDS_NTR16, true, 1, plain);
-    return president_key_of(f.MB, BUILDS_NTR, x16, f.res_nu != 2 ? 1 : 2, plain);
+    if (x16 && f.res_wide) return president_key_of(f.MB, PERSIST_NTR16, true, 1, plain);
+    return president_key_of(f.MB, PERSIST_NTR, x16, f.res_nu != 2 ? 1 : 2, plain);
 }
 
 // The dev pass.  One or two row blocks (R <= 32): the m-blocks of a row tile are split over the four waves, and the rows of a bf16 table
 // stay 16-bit in LDS; two row blocks per wave (R = 72 .. 128) over a bf16 table: exact bf16 x 3 feature products on the bf16 matrix
 // pipe; else the plain build.  no_*: the MFAS_EVAL_NO_* switches
 inline BuildKey eval_key(const PlanFacts& f, int dtype, bool no_x16, bool no_msplit, bool no_b3) {
-    const bool bf16 = dtype == BUILDS_DT_BF16;
+    const bool bf16 = dtype == MFAS_DT_BF16;
     if (f.nrbw == 1 && (f.nrb == 1 || f.nrb == 2) && !no_msplit) return eval_key_of(f.mbe, 1, f.nrb, bf16 && !no_x16, false);
     if (bf16 && f.nrbw == 2 && !no_b3) return eval_key_of(f.mbe, 2, 0, false, true);
     return eval_key_of(f.mbe, f.nrbw, 0, false, false);
@@ -147,12 +146,17 @@ inline std::vector<BuildKey> plan_keys(const PlanFacts& f) {
 #define BUILDS_PRESIDENT_FORMS(ROW, M, P) ROW(M, 4, 0, 1, P) ROW(M, 4, 0, 2, P) ROW(M, 4, 1, 1, P) ROW(M, 4, 1, 2, P) ROW(M, 8, 1, 1, P)
 #define BUILDS_PRESIDENT_ROWS(ROW) BUILDS_PRESIDENT_FORMS(ROW, 1, 0) BUILDS_PRESIDENT_FORMS(ROW, 2, 0) BUILDS_PRESIDENT_FORMS(ROW, 1, 1) \
     BUILDS_PRESIDENT_FORMS(ROW, 2, 1) BUILDS_PRESIDENT_FORMS(ROW, 1, 2) BUILDS_PRESIDENT_FORMS(ROW, 2, 2)
-// k_eval<MBE, NRBW, MSP, XB, B3>: the m-blocks split over the waves (f32 and 16-bit rows), bf16 x 3, plain
+// k_eval<MBE, NRBW, MSP, XB, B3>: the m-blocks split over the waves (f32 and 16-bit rows), bf16 x 3, plain.  Only what an accepted
+// geometry can launch is built.  The tile is 64 rows (MBE = 4) unless (64 * (max(136, Cp + 4) + Rp + 8)) * 4 exceeds 80 KiB, i.e.
+// Rp + max(136, Cp + 4) > 312, and 32 rows (MBE = 2) unless Rp + max(136, Cp + 4) > 632; C <= 256, so max(136, Cp + 4) <= 260.  So:
+//   the split builds (one or two row blocks, Rp <= 32): 32 + 260 = 292 is not over 312 — the tile is always 64 rows, MBE = 4 only;
+//   MBE = 1 (a 16-row tile) needs Rp + 260 > 632, Rp > 372 — only with eight row blocks per wave: (1, 8) and no other MBE = 1 row;
+//   (4, 8): eight row blocks per wave is Rp >= 272, and 272 + 136 = 408 is over 312 — the tile is never 64 rows.
+// (eval_build of a key that is not built gives nullptr: launch_eval answers hipErrorInvalidValue)
 #define BUILDS_EVAL_SPLIT(ROW, M, S) ROW(M, 1, S, 0, 0) ROW(M, 1, S, 1, 0)
-#define BUILDS_EVAL_ROWS(ROW) BUILDS_EVAL_SPLIT(ROW, 4, 1) BUILDS_EVAL_SPLIT(ROW, 4, 2) BUILDS_EVAL_SPLIT(ROW, 2, 1) BUILDS_EVAL_SPLIT(ROW, 2, 2) \
-    BUILDS_EVAL_SPLIT(ROW, 1, 1) BUILDS_EVAL_SPLIT(ROW, 1, 2) ROW(4, 2, 0, 0, 1) ROW(2, 2, 0, 0, 1) ROW(1, 2, 0, 0, 1) \
-    ROW(4, 1, 0, 0, 0) ROW(4, 2, 0, 0, 0) ROW(4, 4, 0, 0, 0) ROW(4, 8, 0, 0, 0) ROW(2, 1, 0, 0, 0) ROW(2, 2, 0, 0, 0) ROW(2, 4, 0, 0, 0) ROW(2, 8, 0, 0, 0) \
-    ROW(1, 1, 0, 0, 0) ROW(1, 2, 0, 0, 0) ROW(1, 4, 0, 0, 0) ROW(1, 8, 0, 0, 0)
+#define BUILDS_EVAL_ROWS(ROW) BUILDS_EVAL_SPLIT(ROW, 4, 1) BUILDS_EVAL_SPLIT(ROW, 4, 2) ROW(4, 2, 0, 0, 1) ROW(2, 2, 0, 0, 1) \
+    ROW(4, 1, 0, 0, 0) ROW(4, 2, 0, 0, 0) ROW(4, 4, 0, 0, 0) ROW(2, 1, 0, 0, 0) ROW(2, 2, 0, 0, 0) ROW(2, 4, 0, 0, 0) ROW(2, 8, 0, 0, 0) \
+    ROW(1, 8, 0, 0, 0)
 
 inline std::vector<BuildKey> table_keys() {
     std::vector<BuildKey> out;

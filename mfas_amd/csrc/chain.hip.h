@@ -934,10 +934,9 @@ struct LeanRes {
     long long corr;     // running correct count
     int bad;            // non-finite loss seen
 };
-#define LEAN_OWN_TILES 7   // slots 0..2: OUT_1..OUT_3, slots 3..6: head class blocks 0..3
+// (LEAN_OWN_TILES, LEAN_SCR — the scratch the two offsets below lie in — and the own-tile counts: records.hip.h)
 #define LEAN_BNF 384       // BatchNorm pair-exchange flags (uint32) inside the scratch: [forward sum | forward squares | backward][parity][tile wave]
 #define LEAN_BNV 400       // the cells' batch variance [cell][16] for the running statistics (chain_lean_tail)
-#define LEAN_SCR 1024      // floats: forward BN exchange [parity][sum | squares][tile][16] | +256: dgamma / dbeta [L][2][16] | +512: backward BN exchange | +768: [tile][cell][mean | rstd][16]
 
 // LDS layout shared by chain_lean and the resident helpers
 template <int MB>
@@ -961,8 +960,8 @@ struct LeanLds {
         scr = lgraw + Bp * 64;                               // cross-wave exchange scratch (LEAN_SCR floats)
         own = scr + LEAN_SCR;        // resident: [W|M|V|T][7 tiles][256], the master copy; otherwise [W|T][7 tiles][256] staged at entry
     }
-    static __host__ __device__ constexpr int own_floats() { return 4 * LEAN_OWN_TILES * 256; }
-    static __host__ __device__ constexpr int stage_floats() { return 2 * LEAN_OWN_TILES * 256; }
+    static __host__ __device__ constexpr int own_floats() { return lean_own_floats(); }
+    static __host__ __device__ constexpr int stage_floats() { return lean_stage_floats(); }
     // tile image of slot s (OUT_{s+1} / head block s-3) as the A operand of the forward products, and its transposed image
     template <bool RES> __device__ __forceinline__ float* wtile(int s) const { return own + s * 256; }
     template <bool RES> __device__ __forceinline__ float* ttile(int s) const { return own + ((RES ? 3 : 1) * LEAN_OWN_TILES + s) * 256; }
@@ -1905,10 +1904,8 @@ __device__ __forceinline__ void lean_res_store(const ChainArgs& a, const int bid
 // sums and the forward and backward column of a cell (activation, BatchNorm, dropout and their gradients).  Every schedule stays bit-identical
 // (tests/test_gpu_parity.py::test_same_group_launch_fuzz_bit_identical, ::test_full_size_properties, ::test_chain_split_bit_identical).
 // ------------------------------------------------------------------------------------------------
-#define XCH_SLOTS 7
-#define XCH_SENT 0xFFFFFFFFu
+#define XCH_SENT 0xFFFFFFFFu      // (XCH_SLOTS, XCH_CAND_FLOATS: records.hip.h)
 #define XCH_SPIN_LIMIT (1u << 21)
-#define XCH_CAND_FLOATS (2 * XCH_SLOTS * 8 * 256)
 
 __device__ __forceinline__ f32x4 xch_wait(const float* base, const int64_t idx, int32_t* status, const int gidx) {
     uint32_t spins = 0;
@@ -1920,13 +1917,6 @@ __device__ __forceinline__ f32x4 xch_wait(const float* base, const int64_t idx, 
         asm volatile("" ::: "memory");          // the load is re-issued every turn
         __builtin_amdgcn_s_sleep(1);
     }
-}
-
-// LDS floats of chain_split<NS> (host: launch size)
-template <int NS> __host__ __device__ constexpr size_t chain_split_lds_floats(int Rp, int Cp) {
-    return (size_t)2 * 16 * (Rp + 4) + (size_t)16 * (Cp + 4) + (size_t)MFAS_MAX_CELLS * (8 / NS) * 16 + 48 + 16 +
-           (size_t)MFAS_MAX_CELLS * (8 / NS) * 256 + (size_t)(MFAS_MAX_CELLS * 5 * (8 / NS) * 16 + Cp) + (size_t)(8 / NS) * 8 * 256 +
-           (size_t)2 * MFAS_MAX_CELLS * (8 / NS) * 256 + (size_t)(8 / NS) * 256;
 }
 
 template <int NS>

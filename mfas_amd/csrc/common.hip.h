@@ -1,6 +1,9 @@
-// common.hip.h — device-side records (SegDesc, TapDesc, CandDev, Geo), small math helpers and LDS row staging
+// common.hip.h — small device math helpers and LDS row staging; HIPCHK.  The records the kernels read (SegDesc, TapDesc, CandDev, Geo)
+// and the sizes they share with the planner are records.hip.h's
 // (part of the single translation unit mfas_hip.hip; see the header comment there and DESIGN.md)
 #pragma once
+#include "records.hip.h"
+#include "hosterr.hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Explicit LDS / global address spaces for pointers whose provenance the compiler cannot see (a buffer picked by a runtime
@@ -15,78 +18,12 @@ template <typename T> __device__ __forceinline__ MFAS_LDS T* as_lds(T* p) { retu
 template <typename T> __device__ __forceinline__ MFAS_GLB T* as_glb(T* p) { return (MFAS_GLB T*)p; }
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-#define KIND_S 0
-#define KIND_V 1
-#define KIND_OUT 2
-#define KIND_HEAD 3
-
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
 #define HIPCHK(x)                                                                                  \
     do {                                                                                           \
         hipError_t e_ = (x);                                                                       \
         if (e_ != hipSuccess)                                                                      \
             return fail(MFAS_EHIP, std::string(#x) + ": " + hipGetErrorString(e_));                \
     } while (0)
-
-// ------------------------------------------------------------------------------------------------
-// Device-side descriptors
-// ------------------------------------------------------------------------------------------------
-struct SegDesc {          // one workgroup of k_sweep / k_pack
-    int32_t cand, kind, cell, tap;
-    int32_t k0, cc;       // first column inside the segment, chunk columns (multiple of 16)
-    int32_t rows_p, width;  // padded rows; FEAT: table row width (elements)
-    int64_t w_off;        // float offset (within a plane) of this chunk: tiles [rb][kb][256]
-    int64_t wt_off;       // OUT/HEAD: float offset in the transposed arena, else -1
-    int32_t part_idx;     // FEAT: chunk index within the cell's partial list
-    int32_t rows, cols;   // true rows (R or C) / true columns of the whole segment
-    int64_t src_off;      // flat-parameter offset of the matrix this segment belongs to
-    int32_t src_ld, src_col0;
-    uint32_t init_seed;   // hash seed of that matrix (device init)
-    float init_bound;
-    int32_t rb0, seg_nrb; // row-split units: first row block of this unit inside the segment, row blocks of the whole segment
-                          // (rows_p = rows of THIS unit; w_off already points at row block rb0 of the chunk)
-    int32_t sub_kb0, sub_nkb; // wide units (wide.hip.h): first k-block of the unit inside this layout chunk, its k-blocks (<= 8); 0 elsewhere
-                          // (the struct, and every kernel's descriptor indexing, stays at 104 bytes)
-};
-static_assert(sizeof(SegDesc) == 104, "SegDesc layout");
-
-#define TAP_MAX_ITEMS 8
-struct TapDesc {          // tap-major workgroup (R < 128): one feature chunk shared by up to 8 segments of that tap
-    int32_t kind, tap, k0, cc;      // modality (KIND_S / KIND_V), tap index, first column, columns
-    int32_t rows_p, width, nitems, _pad;
-    int32_t cand[TAP_MAX_ITEMS], cell[TAP_MAX_ITEMS], part_idx[TAP_MAX_ITEMS];
-    int64_t w_off[TAP_MAX_ITEMS];   // plane offset of each item's chunk: tiles [rb][kb][256]
-};
-
-struct CandDev {
-    int32_t L;
-    int32_t conf[MFAS_MAX_CELLS][3];
-    int64_t seg_off[MFAS_MAX_CELLS][3];   // plane offset of S / V / OUT segment of cell i (-1: none)
-    int32_t seg_cc[MFAS_MAX_CELLS][3];    // chunk columns of that segment
-    int32_t seg_cols[MFAS_MAX_CELLS][3];  // padded columns
-    int64_t head_off;
-    int64_t outT_off[MFAS_MAX_CELLS];     // transposed arena offset of cell i's OUT segment
-    int64_t headT_off;
-    int64_t vec_off;                      // plane offset of the vector block
-    int32_t nch_s[MFAS_MAX_CELLS], nch_v[MFAS_MAX_CELLS];
-    int32_t part_cell_off[MFAS_MAX_CELLS];  // first partial-slot index of cell i
-    int64_t step_off;                     // float offset of this candidate's step buffers
-    uint32_t drop_seed;
-    int32_t gidx;                         // index of this candidate in the population (stats / status slot)
-    // flat (reference state_dict order) offsets of this candidate's parameters
-    int64_t f_alpha, f_W[MFAS_MAX_CELLS], f_b[MFAS_MAX_CELLS], f_bn[MFAS_MAX_CELLS], f_Wc, f_bc;
-    int32_t K_in[MFAS_MAX_CELLS];   // in_features of cell i
-    int32_t _pad2[4];
-};
-
-struct DevStats {
-    double train_loss, dev_loss;
-    long long train_corr, dev_corr;
-};
 
 struct AdamC {
     float ss, bc2s, w1, b2, w2, eps, wd;
@@ -98,28 +35,6 @@ __device__ __forceinline__ AdamC adam_consts(const AdamC& k, const float ss, con
     c.ss = ss; c.bc2s = bc2s; c.w1 = k.w1; c.b2 = k.b2; c.w2 = k.w2; c.eps = k.eps; c.wd = k.wd;
     return c;
 }
-
-struct Geo {             // geometry shared by all candidates of a population
-    int32_t R, C, Rp, Cp, nrb, ncb, B, Bp, MB;
-    int32_t bn, alphas, multitask, use_drop;
-    float drop_scale, bn_eps, bn_mom;
-    uint32_t drop_thr;
-    // per-candidate step-buffer sub-offsets (floats)
-    int64_t sb_part, sb_dy, sb_xo, sb_dlog, sb_sav, sb_yf, sb_gsc, sb_size;
-    int32_t vec_cell_stride;   // 5*Rp + 16
-    int32_t vec_head;          // offset of head bias inside the vector block
-    int32_t sw[MFAS_MAX_TAPS], vw[MFAS_MAX_TAPS];   // table row strides of the taps (width padded to 16)
-    int32_t loss_mode;         // 0 softmax CE + accuracy, 1 weighted BCE + F1-samples
-    float f1_th;
-    int64_t order_stride;      // elements between two candidates' sample-order tables (0: one order shared by the population)
-};
-
-// vector block of a candidate (inside every plane): per cell [b | gamma | beta | rm | rv | alpha(16)], then bc[Cp]
-#define VEC_B 0
-#define VEC_G 1
-#define VEC_BE 2
-#define VEC_RM 3
-#define VEC_RV 4
 
 // the sample-order table candidate `gidx` walks (models/searchable.py:248-250: the reference shuffles per candidate and epoch)
 __device__ __forceinline__ const int32_t* cand_order(const int32_t* order, const Geo& g, int gidx) {
@@ -296,10 +211,7 @@ __device__ __forceinline__ void wg_publish_barrier() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 }
-// Per-(candidate, cell) "dy is out" flags of the same-group fused launch (k_step_same): [candidate][8] uint32, slot i < 4: dy_i of
-// cell i (published after backward cell i, i.e. when the chain no longer reads W_out_{i+1}^T / Wc^T either); the value is the
-// global step index + 1 (monotonic over a train() call)
-#define CELLFLAG_STRIDE 8
+// spins a same-group sweep unit waits for its cell's "dy is out" flag (CELLFLAG_STRIDE: records.hip.h) before it reports the lost dependency
 #define CELLFLAG_SPIN_LIMIT (1u << 21)
 
 // sum over the 4 lane groups that share (lane & 15): column reduction of an MFMA D block

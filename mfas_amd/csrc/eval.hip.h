@@ -21,8 +21,7 @@ struct EvalArgs {
                              // compile-time in builds whose instruction schedule is not the -O3 one: -DMFAS_EVAL_WL_SAFE, the ASAN variant)
 };
 
-#define EVAL_CE 128   // staged feature columns per pass
-
+// (EVAL_CE, the staged feature columns per pass: records.hip.h)
 // MSP: 0, or the number of row blocks (1 / 2) when the m-blocks are split over the waves.  XB (with MSP): bf16 table rows stay 16-bit
 // in the LDS tile (half the store instructions, no store conflicts: 8 consecutive lanes write 128 contiguous bytes) and are widened by
 // the wave that reads them (each element is read by exactly one wave under the split).

@@ -14,13 +14,15 @@
 //            dW = x_t^T dy (f32 MFMA) -> Adam(+L2) update of W/m/v in registers -> store -> immediately
 //            use the new W for the NEXT step's forward partial sums (f32 MFMA).  24 B/param/step = the
 //            algorithmic minimum with state in HBM.
-// Source layout (ONE translation unit; this file includes the rest): common.hip.h (device records, helpers, LDS staging), sweep.hip.h
+// Source layout (ONE translation unit; this file includes the rest): records.hip.h (what host and device share, plain C++: the records
+// the planner fills and the kernels read — SegDesc, TapDesc, CandDev, DevStats, Geo — the sizes both agree on and the LDS formulas both
+// use), hosterr.hip.h (fail() and the last error text), common.hip.h (device helpers, LDS staging, HIPCHK), sweep.hip.h
 // (tile_run, sweep_body, sweep_tap_body), chain.hip.h (chain_body, chain_lean, softmax / BCE rows), wide.hip.h (k_chain_wide / k_sweep_wide:
 // the batch walked in tiles), eval.hip.h (k_eval), pack.hip.h (k_pack, k_vec, k_pool, k_stream_probe), surrogate.hip.h (the search
 // controller's LSTM surrogate: k_surr_grad / k_surr_adam / k_surr_forward and their stateless C ABI); host only: devmem.hip.h (DevBuf: the
 // one owner of device memory — a population's buffers and every call's scratch free themselves; nothing else allocates or frees), plan.hip.h (the switches,
-// validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated; plan_dump.hip.h: the
-// plan as text, test-hooks variant only), launches.hip.h (the
+// validate_inputs, plan_layout: layout, schedule, LDS budgets and work lists decided before anything is allocated — the fourth header,
+// after devmem / builds / launches, that is plain C++17 and that g++ compiles alone: tests/plan_header.py), launches.hip.h (the
 // launches of an epoch as data), builds.hip.h (which build a launch takes, as data: the choice functions, the builds a plan can launch, the
 // tables' row lists), state.hip.h (state in and out, the candidate carry, move, the fallback), train.hip.h (the train call); vote.hip.h (k_vote and the host side of
 // mfas_population_evaluate: members through k_eval, then the vote), tally.hip.h (k_tally: the per-class tallies of
@@ -123,9 +125,6 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_chain(const ChainArgs a) {
 #include "devmem.hip.h"
 #include "builds.hip.h"
 #include "plan.hip.h"
-#ifdef MFAS_TEST_HOOKS
-#include "plan_dump.hip.h"     // mfas_test_plan_dump: the whole plan as text (tests/test_plan_cpu.py); never in the product library
-#endif
 
 // ================================================================================================
 // Host side: C ABI
@@ -286,7 +285,6 @@ static hipError_t set_lds(KT kernel, size_t bytes) {
 // chooses a key (builds.hip.h) and looks its row up; create sets the dynamic-LDS limit of the rows of plan_keys (set_lds_all), the keys a
 // population with that plan can choose.  A key that is not built gives nullptr.
 // ------------------------------------------------------------------------------------------------
-static_assert(BUILDS_NTR == PERSIST_NTR && BUILDS_NTR16 == PERSIST_NTR16 && BUILDS_DT_BF16 == MFAS_DT_BF16, "builds.hip.h restates these");
 typedef void (*StepKernel)(const StepArgs);
 typedef void (*ChainKernel)(const ChainArgs);
 typedef void (*PresidentKernel)(const PersistArgs, const int);

@@ -49,7 +49,6 @@ struct PersistArgs {
 #define PERSIST_SYNC_STRIDE 64          // uint32 words per candidate in the sync area
 #define PERSIST_FLAG(sync, c) ((sync) + (size_t)(c) * PERSIST_SYNC_STRIDE)
 #define PERSIST_CNT(sync, c) ((sync) + (size_t)(c) * PERSIST_SYNC_STRIDE + 32)
-#define PERSIST_LDS_WORDS 32            // LDS words the loop itself uses (behind the bodies' LDS)
 // step-phase timestamps (profiles/r02_persist_trace_k6_r16.log; MFAS_PERSIST_TRACE=1 in the environment allocates the buffer)
 #define PTRACE(slot) do { if (a.trace && tr_on) a.trace[tr_base + (slot)] = wall_clock64(); } while (0)
 #define PTRACE_UNIT(base) do { if (a.trace && un.cand == 0 && t == 12 && tid == 0 && un.index < 64) a.trace[(base) + un.index] = wall_clock64(); } while (0)
@@ -443,9 +442,6 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
         }
     }
 }
-
-#define PERSIST_NTR 4                   // resident units, f32 staging: tiles per wave (cc <= 512 columns)
-#define PERSIST_NTR16 8                 // resident units, 16-bit staging: cc <= 1024 columns
 
 // Roll call: the loops below are only deadlock-free when EVERY workgroup of the schedule is resident at the same time.  That holds
 // when the process owns the GPU (workgroups <= #CUs, one per CU); when another process's kernels hold CUs (or the device is CU-masked),

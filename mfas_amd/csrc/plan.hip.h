@@ -7,9 +7,22 @@
 // lds_budgets -> dev_pass_and_streaming -> choose_schedule (enum Sched: the ONE statement of which of wide / resident / same-group / one
 // group / two groups runs) + schedule_flags -> balanced_split -> group_work_list (tap_major_units, wide_units, same_group_units,
 // row_block_unit) -> unit_dependent_flags (red_in_sweep, defer) -> resident_units_and_roles -> layout_step_buffers (once, after defer).
-// tests/test_plan_cpu.py pins the complete result (plan_dump.hip.h) for some 700 inputs.
-// (part of the single translation unit mfas_hip.hip, included after the kernels: the LDS budgets below name their constants)
+// Plain C++17, the fourth host header of this kind after devmem.hip.h, builds.hip.h and launches.hip.h: it includes what it uses and
+// g++ compiles it alone.  What it shares with the kernels — the records it fills (SegDesc, TapDesc, CandDev, Geo), the sizes and the
+// LDS formulas its budgets name — is records.hip.h; fail() is hosterr.hip.h's.  tests/test_plan_cpu.py pins the complete result for
+// some 700 inputs through a g++ program (tests/plan_header.py, tests/plan_dump.h), also under the address and undefined sanitizers.
 #pragma once
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <math.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+#include "records.hip.h"
+#include "hosterr.hip.h"
+#include "builds.hip.h"      // PlanFacts
 // ================================================================================================
 // Tuning — EVERY environment switch of the library, parsed in ONE place (tuning_from_env) when a population is created or planned
 // and kept in the population: nothing else in this translation unit calls getenv, so a variable that changes after create() cannot
@@ -114,7 +127,7 @@ static int pick_chunk(int cols_p, int target) {
 
 // Everything mfas_population_create refuses about (hp, confs, n_cells, K): shared with mfas_population_plan, so that the query never
 // reports a layout for inputs create() would reject.
-static int validate_inputs(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, int32_t K) {
+inline int validate_inputs(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, int32_t K) {
     if (!hp || !confs || !n_cells || K <= 0) return fail(MFAS_EINVAL, "null argument or K <= 0");
     if (hp->R < 1 || hp->R > 512 || hp->C < 1 || hp->C > 256) return fail(MFAS_EINVAL, "R must be in [1,512], C in [1,256]");
     if (hp->B < 2 || hp->B > 128) return fail(MFAS_EINVAL, "batchsize must be in [2,128]");
@@ -213,7 +226,7 @@ static size_t vec_lds(const Geo& g) { return (size_t)3 * (MFAS_MAX_CELLS * g.vec
 // chain_lean: out_i / dy_i of all cells, logits, misc, reduced sums, vector block, saved activations
 static size_t lean_chain_lds(const Geo& g) {
     return ((size_t)2 * MFAS_MAX_CELLS * g.Bp * 20 + (size_t)g.Bp * (g.Cp + 4) + MFAS_MAX_CELLS * 16 + 3 * g.Bp + 16
-            + (size_t)(g.alphas ? 2 : 1) * MFAS_MAX_CELLS * g.MB * 256 + vec_lds(g) / 4 + LEAN_SCR + 8 + LeanLds<1>::stage_floats() + (size_t)g.Bp * 64) * 4;
+            + (size_t)(g.alphas ? 2 : 1) * MFAS_MAX_CELLS * g.MB * 256 + vec_lds(g) / 4 + LEAN_SCR + 8 + lean_stage_floats() + (size_t)g.Bp * 64) * 4;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -535,7 +548,7 @@ static void lds_budgets(const PlanIn& in, const ChunkPlan& lp, LayoutPlan& pl) {
     pl.lds_chain = base + (pl.yf_in_lds ? yf : 0) + (pl.vec_in_lds ? vec : 0);
     pl.lean_chain = lp.lean_ok;
     if (pl.lean_chain) { pl.lds_chain = lean_chain_lds(g); pl.lds_step = std::max(pl.lds_step, pl.lds_chain); }
-    const size_t lds_rchain = pl.res_chain ? pl.lds_chain + 16 + 4 * (size_t)(LeanLds<1>::own_floats() - LeanLds<1>::stage_floats()) : 0;
+    const size_t lds_rchain = pl.res_chain ? pl.lds_chain + 16 + 4 * (size_t)(lean_own_floats() - lean_stage_floats()) : 0;
     pl.lds_president = ((std::max(lds_rchain, res_unit_lds(in.hp, g, lp.max_fcc, lp.nu)) + 15) & ~(size_t)15) + 4 * PERSIST_LDS_WORDS;
 }
 
@@ -860,7 +873,7 @@ static int plan_layout_as(const mfas_hyper* hp, const int32_t* confs, const int3
 // The plan of a population: the batch-resident schedules wherever they hold the geometry — decided exactly as before the wide path
 // existed, so every such population keeps its layout, kernels and bits — and the wide path exactly where they do not: B > 64, more
 // classes than the batch-resident softmax takes, or a step that does not fit the LDS.
-static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int K, int chunk_cols,
+inline int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int K, int chunk_cols,
                        int n_cus, bool allow_persist, const Tuning& tu, LayoutPlan& pl) {
     if (!batch_resident_refuses(hp)) {
         if (int rc = plan_layout_as(hp, confs, n_cells, drop_seeds, K, chunk_cols, n_cus, allow_persist, tu, false, pl)) return rc;
@@ -870,7 +883,7 @@ static int plan_layout(const mfas_hyper* hp, const int32_t* confs, const int32_t
 }
 
 // what the choice of a launch's build reads from the plan (builds.hip.h)
-static PlanFacts plan_facts(const LayoutPlan& pl) {
+inline PlanFacts plan_facts(const LayoutPlan& pl) {
     PlanFacts f;
     f.wide = pl.wide; f.MB = pl.g.MB; f.lean_chain = pl.lean_chain; f.same_group = pl.same_group; f.chain_split = pl.chain_split;
     f.ngroups = (int)pl.groups.size(); f.nontemporal = pl.nontemporal; f.persist = pl.persist; f.res_wide = pl.res_wide; f.res_nu = pl.res_nu;

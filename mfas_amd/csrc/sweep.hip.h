@@ -108,10 +108,8 @@ __device__ __forceinline__ void tile_run(float* Wp, float* Mp, float* Vp, const 
 // k_sweep — fused dW + Adam + next-step forward.  One workgroup = ALL row blocks of one weight segment
 // over a chunk of `cc` columns: x_t / x_{t+1} / dy are staged ONCE in LDS, then every wave streams whole
 // row blocks (contiguous 1 KiB tiles), requesting the W/m/v tiles of 4 k-blocks before consuming them.
+// (STEP_NW waves, STEP_THREADS: records.hip.h)
 // ------------------------------------------------------------------------------------------------
-#define STEP_NW 8
-#define STEP_THREADS (STEP_NW * 64)
-
 struct SweepArgs {
     const SegDesc* desc;
     const TapDesc* tdesc;   // tap-major work list (may be empty)

@@ -11,18 +11,8 @@
 // (part of the single translation unit mfas_hip.hip; see the header comment there and DESIGN.md)
 #pragma once
 
-#define WIDE_SLICE 64     // batch rows a sweep unit stages at a time
-#define WIDE_KB 8         // k-blocks (of 16 columns) per sweep unit: the dW tiles one wave keeps in registers
-#define WIDE_RBG STEP_NW  // row blocks per sweep unit: one per wave
-#define WIDE_TROWS 32     // batch rows the chain stages at a time (two 16-row tiles)
-
-// LDS floats of the two kernels (plan.hip.h budgets them; the kernels lay their buffers out in this order)
-__host__ __device__ constexpr size_t wide_chain_lds_floats(int Rp, int Cp, int Bp) {
-    return (size_t)WIDE_TROWS * ((Rp > Cp ? Rp : Cp) + 4) + (size_t)WIDE_TROWS * (Cp + 4) + (size_t)MFAS_MAX_CELLS * Rp + 2 * (size_t)Bp + 16 + CHAIN_NW;
-}
-__host__ __device__ constexpr size_t wide_sweep_lds_floats(int cols, int rows) {
-    return (size_t)WIDE_SLICE * ((cols + 16) + (cols + 4) + (rows + 16));
-}
+// (WIDE_SLICE, WIDE_KB, WIDE_RBG, WIDE_TROWS and the LDS floats of the two kernels, wide_chain_lds_floats / wide_sweep_lds_floats:
+//  records.hip.h — the kernels lay their buffers out in the formulas' order)
 
 // Softmax cross-entropy of the <= 32 staged rows (batch rows row0 ...), 16 lanes per row, <= 16 classes per lane (C <= 256): the
 // arithmetic of softmax_rows_nc (chain.hip.h) at any batch size.  dlogits = (softmax - onehot) / nvalid in place, the row's loss in

@@ -69,7 +69,7 @@ def program(mutation=None):
         with open(os.path.join(d, "builds.hip.h"), "w") as f:
             f.write(src.replace(mutation[0], mutation[1]))
         inc = d
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + inc, os.path.join(d, "main.cpp"), "-o", os.path.join(d, "main")])
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + inc, "-I" + CSRC, os.path.join(d, "main.cpp"), "-o", os.path.join(d, "main")])      # (CSRC: records.hip.h beside a mutated copy)
     return os.path.join(d, "main")
 
 

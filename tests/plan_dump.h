@@ -1,10 +1,11 @@
-// plan_dump.hip.h — test hooks only (-DMFAS_TEST_HOOKS, libmfas_hip_hooks.so): the WHOLE LayoutPlan as text, so that tests/test_plan_cpu.py
-// can pin every descriptor, offset, work list and budget of plan_layout() without a device.  One section per part of the plan; structs
-// are written field by field, by name (never as bytes: padding must not enter).  mode 0: the `scalars` section in clear, of every other
-// section its record count and the 64-bit FNV-1a digest of its text; mode 1: every section in clear (what one diffs when a digest moves).
-// Not declared in include/mfas_hip.h, not in the product library.
+// plan_dump.h — the WHOLE LayoutPlan of mfas_amd/csrc/plan.hip.h as text, so that tests/test_plan_cpu.py can pin every descriptor,
+// offset, work list and budget of plan_layout() without a device.  One section per part of the plan; structs are written field by
+// field, by name (never as bytes: padding must not enter).  mode 0: the `scalars` section in clear, of every other section its record
+// count and the 64-bit FNV-1a digest of its text; mode 1: every section in clear (what one diffs when a digest moves).
+// Plain C++17 like the header it prints: part of the g++ program of tests/plan_header.py, of no library.
 #pragma once
 #include <stdarg.h>
+#include "plan.hip.h"
 
 struct PlanText {
     std::string out, sec, name;
@@ -114,11 +115,10 @@ static void dump_group(PlanText& t, const GroupPlan& gr, int gi) {
 }
 
 // The plan of (hp, confs, n_cells, drop_seeds, K, chunk_cols) on a device of n_cus compute units, under the switches of the current
-// environment (tuning_from_env, as mfas_population_plan), as text into buf.  *need receives the bytes the text takes with its
-// terminator; MFAS_EINVAL when cap is smaller (nothing is written then).  No device is touched.
-extern "C" int mfas_test_plan_dump(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int32_t K,
-                                   int32_t chunk_cols, int32_t n_cus, int32_t allow_persist, int32_t mode, char* buf, int64_t cap, int64_t* need) {
-    if (!buf || !need || (mode != 0 && mode != 1)) return fail(MFAS_EINVAL, "null argument or unknown mode");
+// environment (tuning_from_env, as mfas_population_plan), as text into out.
+inline int plan_dump(const mfas_hyper* hp, const int32_t* confs, const int32_t* n_cells, const uint32_t* drop_seeds, int32_t K,
+                     int32_t chunk_cols, int32_t n_cus, int32_t allow_persist, int32_t mode, std::string& out) {
+    if (mode != 0 && mode != 1) return fail(MFAS_EINVAL, "unknown mode");
     if (int vrc = validate_inputs(hp, confs, n_cells, K)) return vrc;
     LayoutPlan pl;
     if (int prc = plan_layout(hp, confs, n_cells, drop_seeds, K, chunk_cols, n_cus, allow_persist != 0, tuning_from_env(), pl)) return prc;
@@ -136,9 +136,7 @@ extern "C" int mfas_test_plan_dump(const mfas_hyper* hp, const int32_t* confs, c
     dump_segs(t, "pdescs", pl.pdescs);
     dump_ints(t, "need", pl.need);
     dump_ints(t, "role", pl.role);
-    *need = (int64_t)t.out.size() + 1;
-    if (*need > cap) return fail(MFAS_EINVAL, "plan dump: buffer too small");
-    memcpy(buf, t.out.c_str(), t.out.size() + 1);
+    out.swap(t.out);
     return MFAS_OK;
 }
 #undef PD_I

@@ -2,8 +2,8 @@
 of a POPULATION call, the parameters snapshot_best leaves, and the status word.
 
 (a) Population dev pass.  REPORT_CASES names every k_eval build the dev pass's choice can reach (builds.hip.h: eval_key, held to each
-    case's build by tests/test_report_cpu.py; the builds no accepted geometry reaches are listed in UNREACHABLE_BUILDS with the
-    reason) with K >= 9 heterogeneous candidates, so that the bf16 x 3 build's 1-D grid takes its interleaved branch (full groups of
+    case's build by tests/test_report_cpu.py; the argument combinations no accepted geometry reaches are not built, builds.hip.h
+    says why) with K >= 9 heterogeneous candidates, so that the bf16 x 3 build's 1-D grid takes its interleaved branch (full groups of
     eight candidates) and its remainder branch.
     E = 2 as two segments; column e of segment e of every candidate through check_dev against ref64 on that candidate's own
     parameters after that epoch.  The candidates' ref64 loss intervals are pairwise disjoint (asserted), so a slot or tile mix-up

@@ -1,4 +1,4 @@
-"""The whole layout plan, pinned on the CPU (plan.hip.h: plan_layout; plan_dump.hip.h: mfas_test_plan_dump of the test-hooks variant).
+"""The whole layout plan, pinned on the CPU (plan.hip.h: plan_layout, compiled by g++ alone with tests/plan_dump.h: tests/plan_header.py).
 
 mfas_population_plan answers eight integers; every kernel reads the rest — descriptor lists, offsets, the group split, tap units, the
 unit order of the same-group launch, the role table, LDS budgets, the step-buffer layout.  Here the dump of the complete plan is
@@ -9,14 +9,16 @@ with every section's digest is profiles/plan_stages.log).  A moved digest is a c
 The inputs are what the suite already trains (by import) plus the edges of every threshold the planner has, every switch, and a seeded
 grid; the test itself asserts that they reach every value of every boolean or enumerated field, that every pinned plan's PlanFacts
 name builds the tables hold (builds.hip.h), and that the six values test_wide_cpu.py pins are the dump's."""
-import ctypes as C
 import functools
 import os
 
 import numpy as np
+import pytest
 
 from oracle import np_oracle as O
 from tests import builds_header as BH
+from tests import devmem_header as DH
+from tests import plan_header as PH
 from tests import axes_cases as AX
 from tests import ref64_cases as G
 from tests import resident_cases as GR
@@ -167,10 +169,10 @@ def all_cases():
 
 
 # ------------------------------------------------------------------------------------------------ the dump
-@functools.lru_cache(maxsize=None)
 def hooks_lib():
-    import __graft_entry__ as ge
-    return C.CDLL(ge.build_variant("hooks", ["-DMFAS_TEST_HOOKS"]))
+    """What dump() asks: the g++ program of tests/plan_header.py.  (The name is from when the dump was an export of the test-hooks
+    library; the test bodies below, which the pins were recorded with, still call it.)"""
+    return PH.program()
 
 
 def fnv64(text):
@@ -181,33 +183,9 @@ def fnv64(text):
 
 
 def dump(lib, case, mode=0):
-    """mfas_test_plan_dump of a case under the case's switches (set the way the plan tests set them: in this process' environment,
-    for the one call)."""
-    K = len(case["confs"])
-    cf, nc = np.zeros((K, 4, 3), np.int32), np.zeros(K, np.int32)
-    for k, c in enumerate(case["confs"]):
-        cf[k, :len(c)], nc[k] = c, len(c)
-    seeds = None if case["seeds"] is None else np.asarray(case["seeds"], np.uint32)
-    hc, need = case["hp"].to_c(), C.c_int64(0)
-    outer = {k: os.environ.pop(k) for k in list(os.environ) if k.startswith("MFAS_")}      # (the pins hold for the case's switches alone)
-    os.environ.update(case["env"])
-    try:
-        cap = 1 << 16
-        for _ in range(2):
-            buf = C.create_string_buffer(cap)
-            rc = lib.mfas_test_plan_dump(C.byref(hc), C.c_void_p(cf.ctypes.data), C.c_void_p(nc.ctypes.data),
-                                         C.c_void_p(seeds.ctypes.data if seeds is not None else None), C.c_int32(K), C.c_int32(case["cc"]),
-                                         C.c_int32(case["n_cus"]), C.c_int32(int(case["persist"])), C.c_int32(mode), buf, C.c_int64(cap),
-                                         C.byref(need))
-            if rc == 0 or need.value <= cap:
-                break
-            cap = need.value
-    finally:
-        for k in case["env"]:
-            os.environ.pop(k, None)
-        os.environ.update(outer)
-    assert rc == 0, (case["id"], rc)
-    return buf.value.decode()
+    """The plan dump of a case under the case's switches and no other (tests/plan_header.py sets the program's environment)."""
+    assert lib == PH.program()
+    return PH.dumps([case], mode)[0][0]
 
 
 def parse(text):
@@ -224,8 +202,7 @@ def parse(text):
 
 @functools.lru_cache(maxsize=None)
 def all_dumps():
-    lib = hooks_lib()
-    return {c["id"]: dump(lib, c) for c in all_cases()}
+    return dict(zip((c["id"] for c in all_cases()), PH.dumps(all_cases())[0]))
 
 
 # ------------------------------------------------------------------------------------------------ the tests
@@ -329,6 +306,57 @@ def test_the_plan_query_pins_are_the_dumps():
         assert d["wide-" + cid]["wide"] == "1", cid
 
 
+def test_the_planner_that_ships_answers_what_the_pinned_one_does():
+    """The pins are of plan.hip.h as g++ compiles it; the library holds it as clang does.  Every pinned case the product library's
+    mfas_population_plan can be asked — 256 compute units (what the query assumes without a device, and what an MI355X has), the
+    resident schedule allowed — under its switches: persistent, resident units and workgroups, units per workgroup, chunk, lean, wide
+    and K are the dump's scalars."""
+    from mfas_amd.engine import plan_population
+    asked = [c for c in all_cases() if c["n_cus"] == 256 and c["persist"]]
+    assert len(asked) >= 300 and len({tuple(sorted(c["env"].items())) for c in asked}) >= 20
+    outer = {k: os.environ.pop(k) for k in list(os.environ) if k.startswith("MFAS_")}
+    try:
+        for c in asked:
+            os.environ.update(c["env"])
+            try:
+                plan = plan_population(c["hp"], c["confs"], "cuda:0", c["cc"])
+            finally:
+                for k in c["env"]:
+                    os.environ.pop(k, None)
+            assert plan["compute_units"] == 256, plan
+            s = parse(all_dumps()[c["id"]])[0]
+            want = dict(persistent=s["persist"], resident_units=s["nres"], resident_workgroups=s["nres_wg"], units_per_workgroup=s["res_nu"],
+                        chunk_cols=s["chunk"], lean_chain=s["lean_chain"], wide=s["wide"], candidates=s["K"])
+            assert {k: int(plan[k]) for k in want} == {k: int(v) for k, v in want.items()}, (c["id"], plan, want)
+    finally:
+        os.environ.update(outer)
+
+
+def test_the_planner_under_address_and_undefined_sanitizers():
+    """The same program built with -fsanitize=address,undefined -fno-sanitize-recover=all and run directly — a stand-alone executable,
+    no sanitizer runtime is preloaded into anything — over ALL cases (some 30 s in all, the build included: profiles/plan_header.log):
+    it ends clean, reports nothing, and every plan is still the pinned one."""
+    why = DH.sanitizer_missing()
+    if why:
+        pytest.skip(why)
+    texts, err = PH.dumps(all_cases(), flags=PH.SANITIZE)
+    assert "ERROR" not in err and "runtime error" not in err, err[-4000:]
+    moved = [c["id"] for c, t in zip(all_cases(), texts) if fnv64(t) != PINNED[c["id"]]]
+    assert len(texts) == len(PINNED) and not moved, (len(moved), moved[:20])
+
+
+@pytest.mark.parametrize("what,mutation", [
+    ("pick_chunk: a chunk that does not divide the padded columns", ("if (cols_p % c == 0) best = c;", "best = c;")),
+    ("balanced_split: the first group stops one candidate late at an exact half", ("if (run >= tot / 2) break;", "if (run > tot / 2) break;")),
+], ids=["pick_chunk", "balanced_split"])
+def test_a_wrong_planner_moves_pinned_digests(what, mutation):
+    """plan.hip.h with one piece of text replaced, over the same cases: pinned digests move, and the message a failure of
+    test_every_plan_is_the_pinned_one would carry names the cases."""
+    texts = PH.dumps(all_cases(), mutation=mutation)[0]
+    moved = [c["id"] for c, t in zip(all_cases(), texts) if fnv64(t) != PINNED[c["id"]]]
+    assert moved, what
+    message = repr((len(moved), moved[:20], texts[[c["id"] for c in all_cases()].index(moved[0])]))
+    assert moved[0] in message and all(m in PINNED for m in moved)
 
 
 # ------------------------------------------------------------------------------------------------ the pins
