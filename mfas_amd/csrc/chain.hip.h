@@ -934,9 +934,7 @@ struct LeanRes {
     long long corr;     // running correct count
     int bad;            // non-finite loss seen
 };
-// (LEAN_OWN_TILES, LEAN_SCR — the scratch the two offsets below lie in — and the own-tile counts: records.hip.h)
-#define LEAN_BNF 384       // BatchNorm pair-exchange flags (uint32) inside the scratch: [forward sum | forward squares | backward][parity][tile wave]
-#define LEAN_BNV 400       // the cells' batch variance [cell][16] for the running statistics (chain_lean_tail)
+// (LEAN_OWN_TILES, LEAN_SCR and the own-tile counts: records.hip.h; the parts of the scratch, LeanScr: lds.hip.h)
 
 // LDS layout shared by chain_lean and the resident helpers
 template <int MB>
@@ -1260,7 +1258,7 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
         }
     }
     if constexpr (!RES) {
-        if (tid < 16) reinterpret_cast<uint32_t*>(ll.scr + LEAN_BNF)[tid] = 0u;   // (one step per launch: LDS starts undefined; resident: lean_res_load)
+        if (tid < 16) reinterpret_cast<uint32_t*>(ll.scr + LeanScr::bnf)[tid] = 0u;   // (one step per launch: LDS starts undefined; resident: lean_res_load)
         if (tid < nvec) { vec_l[tid] = vw; vec_l[nvec + tid] = vm; vec_l[2 * nvec + tid] = vv; }
         *reinterpret_cast<f32x4*>(ll.own + (wave << 8) + lane * 4) = st0;
         if (wave + 1 < LEAN_OWN_TILES) *reinterpret_cast<f32x4*>(ll.own + ((LEAN_OWN_TILES + wave + 1) << 8) + lane * 4) = st1;
@@ -1287,13 +1285,13 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
     };
 
     // ------------------------------------------------------------------ forward, in the tile waves' registers
-    float* bnw = ll.scr;                                     // BN exchange: [parity][sum | sum of squares][tile][16]
+    float* bnw = ll.scr + LeanScr::bn_fwd;                                  // BN exchange: [parity][sum | sum of squares][tile][16]
     // BatchNorm with TWO batch tiles (B = 17 .. 32): the column statistics need both tile waves' partial sums.  Round 6: the two waves
     // exchange them PAIRWISE — data, then a sequence number behind it (LDS executes a wave's instructions in order; release / acquire at
     // workgroup scope = a wait for the wave's own LDS operations), the partner polls the number — instead of through workgroup barriers
     // that made the tile waves wait for the six waves summing slabs: 3 barriers per cell were 12 of the 22.6 us of a BatchNorm step.
     // Parity double-buffering of the regions is enough: a wave cannot pass exchange k + 1 before its partner has finished reading k.
-    uint32_t* bnf = reinterpret_cast<uint32_t*>(ll.scr + LEAN_BNF);
+    uint32_t* bnf = reinterpret_cast<uint32_t*>(ll.scr + LeanScr::bnf);
     const uint32_t bnseq = (uint32_t)cs.gstep * (uint32_t)MFAS_MAX_CELLS + 1u;
     // (the LDS unit executes ONE wave's instructions in issue order — data store, then number store: no wait between them; and a wave's
     //  data read is issued only after its poll has returned the number: compiler barriers keep that order, no s_waitcnt is added)
@@ -1309,8 +1307,8 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
         asm volatile("" ::: "memory");
     };
     static_assert(MB <= 2, "pairwise exchange: two tile waves");
-    float* gv2 = ll.scr + 256;                               // [cell][dgamma | dbeta][16]
-    float* bst = ll.scr + 768 + (is_tw ? wave : 0) * 128;     // this tile wave's copy of every cell's batch mean | rstd: [cell][2][16]
+    float* gv2 = ll.scr + LeanScr::gv2;                             // [cell][dgamma | dbeta][16]
+    float* bst = ll.scr + LeanScr::bst + (is_tw ? wave : 0) * 128;    // this tile wave's copy of every cell's batch mean | rstd: [cell][2][16]
     f32x4 av[MFAS_MAX_CELLS];                                 // activations: all the backward needs again in registers (x-hat is recomputed
                                                               // from the batch statistics, the alpha differences wait in the dead sums plane)
     f32x4 o_prev = z4;
@@ -1412,7 +1410,7 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
                     }
                     // (running statistics: chain_lean_tail steps them from this variance and the mean above, after dy is out — as four
                     //  serial element updates on tile wave 0 they delayed BOTH tile waves of every forward cell)
-                    if (wave == 0 && l15 == 0) *reinterpret_cast<f32x4*>(ll.scr + LEAN_BNV + i * 16 + r0) = var;
+                    if (wave == 0 && l15 == 0) *reinterpret_cast<f32x4*>(ll.scr + LeanScr::bnv + i * 16 + r0) = var;
                 }
             }
             if (is_tw) {
@@ -1612,7 +1610,10 @@ __device__ __forceinline__ void chain_lean(const ChainArgs& a, const ChainStep& 
             }
             f32x4 dz = d;
             if (f_bn) {
-                float* ex = bnw + 512 + (i & 1) * 128;     // (not the forward's region: no barrier separates the last forward cell's reads from these writes)
+                // (not the forward's region: no barrier separates the last forward cell's reads from these writes.  Spelled from bnw, the
+                //  forward's base, on purpose: as `ll.scr + LeanScr::bn_bwd` the MB = 2 lean kernels compile to other, longer code —
+                //  profiles/lds_layouts.log, section 1.  Do not simplify without comparing the code objects.)
+                float* ex = bnw + (LeanScr::bn_bwd - LeanScr::bn_fwd) + (i & 1) * 128;
                 f32x4 dbet = p0, dgam = p1;
                 if constexpr (MB > 1) {
                     if (is_tw) {
@@ -1674,7 +1675,7 @@ __device__ __forceinline__ void chain_lean_tail(const ChainArgs& a, const ChainS
     const float* dy_l = ll.dy_l;
     const float* red_l = ll.red_l;
     float* vec_l = ll.vec_l;
-    const float* gv2 = ll.scr + 256;
+    const float* gv2 = ll.scr + LeanScr::gv2;
     const int64_t cvec_off = cd.vec_off;
     const int cgidx = cd.gidx;
     const AdamC ac = adam_consts(a.ac, cs.ss, cs.bc2s);
@@ -1689,7 +1690,7 @@ __device__ __forceinline__ void chain_lean_tail(const ChainArgs& a, const ChainS
     };
     if (g.bn && tid < L * 16 && (tid & 15) < R) {      // running statistics: momentum 0.1, unbiased variance (torch BatchNorm1d, train mode)
         const int i = tid >> 4, c = tid & 15, vbl = i * g.vec_cell_stride;
-        const float mu = ll.scr[768 + i * 32 + c], var = ll.scr[LEAN_BNV + i * 16 + c], nf = (float)cs.nvalid;
+        const float mu = ll.scr[LeanScr::bst + i * 32 + c], var = ll.scr[LeanScr::bnv + i * 16 + c], nf = (float)cs.nvalid;
         float rm = vecW[vbl + VEC_RM * Rp + c], rv = vecW[vbl + VEC_RV * Rp + c];
         const float unb = var * (nf / (nf - 1.0f));
         rm += g.bn_mom * (mu - rm);
@@ -1808,7 +1809,7 @@ __device__ __forceinline__ void lean_res_load(const ChainArgs& a, const int bid,
         *reinterpret_cast<f32x4*>(ll.own + (3 * LEAN_OWN_TILES + s) * 256 + lane * 4) = t;
     }
     if (tid == CHAIN_THREADS - 64) { rs.loss = 0.0; rs.corr = 0; rs.bad = 0; }     // (rs may live in LDS: one writer, the lane that accumulates)
-    if (tid < 16) reinterpret_cast<uint32_t*>(ll.scr + LEAN_BNF)[tid] = 0u;       // BatchNorm pair-exchange flags (chain_lean): sequence numbers start at 1
+    if (tid < 16) reinterpret_cast<uint32_t*>(ll.scr + LeanScr::bnf)[tid] = 0u;       // BatchNorm pair-exchange flags (chain_lean): sequence numbers start at 1
     __syncthreads();
 }
 

@@ -3,6 +3,7 @@
 // (part of the single translation unit mfas_hip.hip; see the header comment there and DESIGN.md)
 #pragma once
 #include "records.hip.h"
+#include "lds.hip.h"
 #include "hosterr.hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -166,7 +166,7 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
     const int K = a.nchain;
     uint32_t* abortw = a.sync + (size_t)K * PERSIST_SYNC_STRIDE;
     float* wred = lds + (size_t)NU * 2 * a.res_buf_words;      // [8 waves][MB][256] cross-wave reduction of the forward partial
-    int* nxt = ldsw + 8;                                          // next step of my u-th unit
+    int* nxt = ldsw + PresWords::next;                                        // next step of my u-th unit
 
     ResUnit U[NU];
     f32x4 w4[NU][NTR], m4[NU][NTR], v4[NU][NTR];
@@ -234,9 +234,9 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) {
                 int old = 0;
-                if constexpr (MB > 1) old = __hip_atomic_fetch_add(ldsw + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if constexpr (MB > 1) old = __hip_atomic_fetch_add(ldsw + PresWords::arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (old == MB - 1) {
-                    if constexpr (MB > 1) __hip_atomic_store(ldsw + 4, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if constexpr (MB > 1) __hip_atomic_store(ldsw + PresWords::arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
@@ -266,7 +266,7 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
     //  already serves its other unit — was a measured negative, 15.1 / 15.5 -> 16.1 / 16.4 us per step at 22 / 28 candidates, and is gone:
     //  profiles/r05_defer_ab.log, DESIGN_HISTORY.md.)
     constexpr int POLL_TID = STEP_THREADS - 64;      // the unit loop's poller: lane 0 of the last wave (waves 0 .. MB-1 drain the slab stores)
-    if (tid == 0) ldsw[4] = 0;
+    if (tid == 0) ldsw[PresWords::arrive] = 0;
 
     // ---- prologue per unit: forward partial sums of batch 0 (no update), then batch 1 staged
 #pragma unroll
@@ -360,10 +360,10 @@ __device__ __forceinline__ void sweep_resident(const PersistArgs& a, const int w
                     break;
                 }
             }
-            ldsw[0] = pick;
+            ldsw[PresWords::pick] = pick;
         }
         __syncthreads();
-        const int pick = ldsw[0];
+        const int pick = ldsw[PresWords::pick];
         if (pick == -3) return;
         if (pick < 0) break;
         const int t = nxt[pick];
@@ -470,10 +470,10 @@ __device__ __forceinline__ bool persist_roll_call(uint32_t* sync, const int K, c
                 }
             } else __builtin_amdgcn_s_sleep(8);
         }
-        ldsw[1] = ok;
+        ldsw[PresWords::roll] = ok;
     }
     __syncthreads();
-    return ldsw[1] != 0;
+    return ldsw[PresWords::roll] != 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -501,8 +501,8 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_president(const PersistArgs
     }
     uint32_t* abortw = a.sync + (size_t)K * PERSIST_SYNC_STRIDE;
     const uint32_t need = (uint32_t)a.need[bid];
-    LeanRes& rs = *reinterpret_cast<LeanRes*>(ldsw + 16);   // the epoch's running statistics: LDS words 16..21 (as registers of one lane
-                                                             // they were live across the whole step loop in every wave, and spilled)
+    LeanRes& rs = *reinterpret_cast<LeanRes*>(ldsw + PresWords::stats);   // the epoch's running statistics (as registers of one lane they
+                                                                           // were live across the whole step loop in every wave, and spilled)
     lean_res_load<MB>(a.ca, bid, lds, rs);
     const LeanPre lpre = lean_pre<MB>(a.ca, bid);
     uint32_t keep = lean_keep_bits<MB>(a.ca.cands[bid], a.ca.g, a.gstep0);     // dropout keep-bits and labels of the step about to run
@@ -520,7 +520,7 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_president(const PersistArgs
         cs.epoch = a.epoch;
         cs.ss = a.scal[2 * (int64_t)cs.gstep];
         cs.bc2s = a.scal[2 * (int64_t)cs.gstep + 1];
-        if (!wg_wait_ge(PERSIST_CNT(a.sync, bid), need * (uint32_t)(t + 1), abortw, ldsw)) return;
+        if (!wg_wait_ge(PERSIST_CNT(a.sync, bid), need * (uint32_t)(t + 1), abortw, ldsw + PresWords::wait)) return;
         PTRACE(1);
         chain_lean<MB, 2, 16, PLAIN>(a.ca, cs, bid, lds, lpre, keep, labp);
         PTRACE(2);

@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 #include "records.hip.h"
+#include "lds.hip.h"
 #include "hosterr.hip.h"
 #include "builds.hip.h"      // PlanFacts
 // ================================================================================================
@@ -218,7 +219,7 @@ static size_t sweep_unit_lds_double(const Geo& g, const SegDesc& d) {
 }
 // the wide path (wide.hip.h): a sweep unit's batch slice of x_t, x_{t+1} and dy; the chain's rows in flight, logits and statistics
 static size_t wide_unit_lds(const SegDesc& d) {
-    return wide_sweep_lds_floats(std::min(16 * WIDE_KB, d.cc), std::min(16 * WIDE_RBG, d.rows_p)) * 4;
+    return (size_t)wide_sweep_lds(0, std::min(16 * WIDE_KB, d.cc), std::min(16 * WIDE_RBG, d.rows_p)).total * 4;
 }
 static size_t wide_chain_lds(const Geo& g) { return wide_chain_lds_floats(g.Rp, g.Cp, g.Bp) * 4; }
 // a candidate's vector block, three planes

@@ -1,7 +1,8 @@
 // records.hip.h — what the host and the kernels SHARE, stated once: the records the planner (plan.hip.h) fills and the kernels read
-// (SegDesc, TapDesc, CandDev, DevStats, Geo), the sizes both sides must agree on, and the LDS formulas the planner budgets with and the
-// kernels lay their buffers out by.  Plain C++17 (no HIP include, no device code): the device headers include it, and so do the pure
-// host headers plan.hip.h and builds.hip.h, which g++ compiles alone (tests/plan_header.py, tests/builds_header.py).
+// (SegDesc, TapDesc, CandDev, DevStats, Geo), the sizes both sides must agree on, and the LDS formulas the planner budgets with where a
+// kernel still walks its LDS itself (the layouts both sides read are lds.hip.h).  Plain C++17 (no HIP include, no device code): the
+// device headers include it, and so do the pure host headers plan.hip.h and builds.hip.h, which g++ compiles alone
+// (tests/plan_header.py, tests/builds_header.py).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -112,7 +113,7 @@ struct Geo {             // geometry shared by all candidates of a population
 #define PERSIST_NTR16 8                 // resident units, 16-bit staging: cc <= 1024 columns
 
 #define LEAN_OWN_TILES 7   // slots 0..2: OUT_1..OUT_3, slots 3..6: head class blocks 0..3
-#define LEAN_SCR 1024      // floats: forward BN exchange [parity][sum | squares][tile][16] | +256: dgamma / dbeta [L][2][16] | +512: backward BN exchange | +768: [tile][cell][mean | rstd][16]
+#define LEAN_SCR 1024      // floats of chain_lean's cross-wave exchange scratch (its parts by name: lds.hip.h, LeanScr)
 // chain_lean's own-tile area (LeanLds<MB>::own_floats / stage_floats): resident [W|M|V|T][7 tiles][256], otherwise [W|T] staged at entry
 MFAS_HD constexpr int lean_own_floats() { return 4 * LEAN_OWN_TILES * 256; }
 MFAS_HD constexpr int lean_stage_floats() { return 2 * LEAN_OWN_TILES * 256; }
@@ -122,12 +123,9 @@ MFAS_HD constexpr int lean_stage_floats() { return 2 * LEAN_OWN_TILES * 256; }
 #define WIDE_RBG STEP_NW  // row blocks per sweep unit: one per wave
 #define WIDE_TROWS 32     // batch rows the chain stages at a time (two 16-row tiles)
 
-// LDS floats of the two wide kernels (plan.hip.h budgets them; the kernels lay their buffers out in this order)
+// LDS floats of k_chain_wide (plan.hip.h budgets them; k_sweep_wide has its layout in lds.hip.h)
 MFAS_HD constexpr size_t wide_chain_lds_floats(int Rp, int Cp, int Bp) {
     return (size_t)WIDE_TROWS * ((Rp > Cp ? Rp : Cp) + 4) + (size_t)WIDE_TROWS * (Cp + 4) + (size_t)MFAS_MAX_CELLS * Rp + 2 * (size_t)Bp + 16 + STEP_NW;
-}
-MFAS_HD constexpr size_t wide_sweep_lds_floats(int cols, int rows) {
-    return (size_t)WIDE_SLICE * ((cols + 16) + (cols + 4) + (rows + 16));
 }
 
 #define EVAL_CE 128   // staged feature columns per pass

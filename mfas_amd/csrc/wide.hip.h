@@ -11,8 +11,8 @@
 // (part of the single translation unit mfas_hip.hip; see the header comment there and DESIGN.md)
 #pragma once
 
-// (WIDE_SLICE, WIDE_KB, WIDE_RBG, WIDE_TROWS and the LDS floats of the two kernels, wide_chain_lds_floats / wide_sweep_lds_floats:
-//  records.hip.h — the kernels lay their buffers out in the formulas' order)
+// (WIDE_SLICE, WIDE_KB, WIDE_RBG, WIDE_TROWS and the LDS floats of k_chain_wide, wide_chain_lds_floats: records.hip.h — the kernel lays
+//  its buffers out in the formula's order; k_sweep_wide takes its buffers from wide_sweep_lds, lds.hip.h)
 
 // Softmax cross-entropy of the <= 32 staged rows (batch rows row0 ...), 16 lanes per row, <= 16 classes per lane (C <= 256): the
 // arithmetic of softmax_rows_nc (chain.hip.h) at any batch size.  dlogits = (softmax - onehot) / nvalid in place, the row's loss in
@@ -465,10 +465,11 @@ __global__ void __launch_bounds__(STEP_THREADS, 2) k_sweep_wide(const StepArgs s
     const int l15 = lane & 15, lg = lane >> 4;
     const int MB = g.MB, Bp = g.Bp;
     const int nrbg = d.rows_p >> 4, nkbl = d.cc >> 4, kbu0 = d.sub_kb0, nkbu = d.sub_nkb, ccu = nkbu * 16, col0 = d.k0 + kbu0 * 16;
-    const int ST = ccu + 16, SN = ccu + 4, SD = d.rows_p + 16;
-    float* xt = lds;
-    float* xn = xt + WIDE_SLICE * ST;
-    float* dyl = xn + WIDE_SLICE * SN;
+    const WideSweepLds<float*> m = wide_sweep_lds(lds, ccu, d.rows_p);    // (lds.hip.h)
+    const int ST = m.ST, SN = m.SN, SD = m.SD;
+    float* xt = m.xt.at;
+    float* xn = m.xn.at;
+    float* dyl = m.dy.at;
     const bool feat = d.kind <= KIND_V;
     const bool upd = a.do_update != 0;
     const bool fwd = (a.do_forward != 0) && feat;

@@ -92,10 +92,11 @@ def case_text(case, mode):
     return "\n".join([" ".join(map(str, head)), " ".join(words), *rows, " ".join(str(int(s)) for s in (seeds or []))]) + "\n"
 
 
-def dumps(cases, mode=0, mutation=None, flags=()):
+def dumps(cases, mode=0, mutation=None, flags=(), exe=None):
     """-> (texts, stderr): the dump of every case, in the cases' order, and what the runs wrote to stderr.  One run of the program —
-    directly, as a stand-alone executable — per distinct env."""
-    exe = program(mutation, tuple(flags))
+    directly, as a stand-alone executable — per distinct env.  exe: another build of the same program (tests/lds_header.py's, over a
+    changed lds.hip.h) in place of program(mutation, flags)."""
+    exe = exe or program(mutation, tuple(flags))
     by_env, texts, errs = {}, {}, []
     for c in cases:
         by_env.setdefault(tuple(sorted(c["env"].items())), []).append(c)
