@@ -263,6 +263,23 @@ int mfas_population_forward_train(mfas_population* pop, int32_t k, const mfas_ta
 int mfas_population_backward(mfas_population* pop, int32_t k, const mfas_table* table, int64_t row0, int32_t nrows,
                              int32_t step_index, const float* dlogits);
 
+/* mfas_population_backward, and the gradients of the same loss with respect to the feature TAPS of the batch as well: the reference's
+ * module is an ordinary nn.Module whose inputs get gradients (Searchable_Skeleton_Image_Net.forward under model.train(True),
+ * models/search/ntu_searchable.py:206-247 of the reference, behind a backbone, adapter or projection that learns).  Everything
+ * mfas_population_backward does, this call does identically — parameter gradients in the first-moment slots, moments scratch, running
+ * statistics moved.  In addition, for every non-NULL ds[j] / dv[j] it writes d loss / d tap as a row-major (nrows, width) float32
+ * array with leading dimension s_sizes[j] / v_sizes[j]: the sum over the cells i of candidate k that select the tap, ascending i, of
+ * scale_i * dy_i * W_i[:, tap columns], scale_i = sigmoid(alpha_i) for S and 1 - sigmoid(alpha_i) for V with alphas, 1 without (one
+ * k_tap_grad launch behind the backward chain, before the call's one synchronise; fixed summation order: the same bits on every run,
+ * whichever other taps are requested).  A requested tap no cell of candidate k selects receives zeros.  ds / dv are HOST arrays of
+ * MFAS_MAX_TAPS DEVICE pointers; either array may be NULL, and with no pointer set the call IS mfas_population_backward.
+ * MFAS_EINVAL, naming the slot, with nothing launched and nothing changed: a non-NULL pointer for a slot of width 0; and everything
+ * mfas_population_backward refuses.  One candidate and one batch per call; float32 output only. */
+int mfas_population_backward_taps(mfas_population* pop, int32_t k, const mfas_table* table, int64_t row0, int32_t nrows,
+                                  int32_t step_index, const float* dlogits,
+                                  float* const* ds /* HOST [MFAS_MAX_TAPS] of DEVICE (nrows, s_sizes[j]) or NULL */,
+                                  float* const* dv /* likewise, v_sizes[j] */);
+
 /* Timing of the dominant kernel (fused cell sweep) over the last train() call, measured with HIP
  * events on the population's stream: number of launches, summed milliseconds, and the algorithmic
  * HBM bytes of one update+forward launch (24*P_tiles + feature bytes). */

@@ -68,6 +68,7 @@ def lib():
     L.mfas_population_forward.argtypes = [P, C.c_int32, C.POINTER(mfas_table), C.c_int64, C.c_int64, P, P]
     L.mfas_population_forward_train.argtypes = [P, C.c_int32, C.POINTER(mfas_table), C.c_int64, C.c_int32, C.c_int32, P]
     L.mfas_population_backward.argtypes = [P, C.c_int32, C.POINTER(mfas_table), C.c_int64, C.c_int32, C.c_int32, P]
+    L.mfas_population_backward_taps.argtypes = L.mfas_population_backward.argtypes + [C.POINTER(P), C.POINTER(P)]
     L.mfas_population_sweep_profile.argtypes = [P, P, P, P]
     L.mfas_population_schedule.argtypes = [P, P]
     L.mfas_population_plan.argtypes = [C.POINTER(mfas_hyper), P, P, C.c_int32, C.c_int32, C.c_int32, P]
@@ -107,7 +108,7 @@ EXPORTS = ["mfas_last_error", "mfas_version", "mfas_population_create", "mfas_po
            "mfas_population_plan", "mfas_population_backward", "mfas_range_push", "mfas_range_pop", "mfas_population_init_torch_streams", "mfas_tuning_describe",
            "mfas_population_train_from", "mfas_population_set_state", "mfas_population_get_progress", "mfas_population_set_progress",
            "mfas_population_move", "mfas_population_launch_record", "mfas_population_evaluate", "mfas_population_evaluate_report",
-           "mfas_surrogate_param_count", "mfas_surrogate_scratch_bytes", "mfas_surrogate_train", "mfas_surrogate_forward"]
+           "mfas_population_backward_taps", "mfas_surrogate_param_count", "mfas_surrogate_scratch_bytes", "mfas_surrogate_train", "mfas_surrogate_forward"]
 
 
 def tuning() -> dict:

@@ -519,6 +519,7 @@ static hipError_t launch_eval(mfas_population* p, const EvalArgs& a, int ncand, 
 // The rest of the host side — host-only headers, included like plan.hip.h — and the C ABI over it
 #include "launches.hip.h"
 #include "state.hip.h"
+#include "tapgrad.hip.h"
 #include "train.hip.h"
 #include "vote.hip.h"
 #include "tally.hip.h"
@@ -656,6 +657,12 @@ extern "C" int mfas_population_forward_train(mfas_population* p, int32_t k, cons
 extern "C" int mfas_population_backward(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0, int32_t nrows,
                                         int32_t step_index, const float* dlogits) {
     return single_batch(p, k, tab, row0, nrows, step_index, nullptr, dlogits);
+}
+
+extern "C" int mfas_population_backward_taps(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0, int32_t nrows,
+                                             int32_t step_index, const float* dlogits, float* const* ds, float* const* dv) {
+    if (!dlogits) return fail(MFAS_EINVAL, "bad argument");
+    return single_batch(p, k, tab, row0, nrows, step_index, nullptr, dlogits, ds, dv);      // (no pointer set: mfas_population_backward)
 }
 
 extern "C" int mfas_stream_probe(int64_t bytes_per_plane, int32_t iters, double* gb_per_s) {

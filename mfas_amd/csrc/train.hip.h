@@ -498,8 +498,10 @@ static int train_impl(mfas_population* p, const mfas_table* train, const mfas_ta
 // One batch through candidate k in TRAIN mode: forward only (logits out), or forward + backward of an external loss
 // (dlogits in): then every parameter's Adam first-moment slot receives its exact GRADIENT and nothing else changes — the step
 // runs with beta1 = 0 (m <- m + 1 * (g - m) = g), weight decay 0 and learning rate 0 (w <- w - 0 * m / denom = w).
+// ds / dv (backward only; HOST [MFAS_MAX_TAPS] of DEVICE pointers or NULL): the gradients of those taps too — one k_tap_grad launch
+// (tapgrad.hip.h) behind the chain's dy, before the call's one synchronise; with no pointer set nothing of it runs.
 static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, int64_t row0, int32_t nrows, int32_t step_index,
-                        float* logits, const float* dlogits) {
+                        float* logits, const float* dlogits, float* const* ds = nullptr, float* const* dv = nullptr) {
     if (!p || (!logits && !dlogits) || k < 0 || k >= p->K || row0 < 0) return fail(MFAS_EINVAL, "bad argument");
     if (int rc = check_table(p, tab, false)) return rc;
     const LayoutPlan& pl = p->plan;
@@ -526,6 +528,8 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
     if (!pl.wide)
         for (int j = pl.desc_start[k]; j < pl.desc_start[k + 1]; ++j) lds_need = std::max(lds_need, sweep_unit_lds(g, pl.descs[j]));
     if (lds_need > 150 * 1024) return fail(MFAS_EINVAL, "train-mode forward: this population's units are too wide for the streaming kernels");
+    TapGradCall tg;      // (the last thing that can refuse: its work list is uploaded before anything is launched)
+    if (dlogits && (ds || dv)) if (int rc = tap_grad_prepare(pl, p->hp, k, ds, dv, tg)) return rc;
     const StepKernel sweep_k = step_build(single_batch_step_key(plan_facts(pl))).fn;
     if (lds_need > pl.lds_step) HIPCHK(set_lds(sweep_k, lds_need));
     auto sweep = [&]() { launch(sweep_k, nsw, lds_need, p->stream, st); };
@@ -544,6 +548,7 @@ static int single_batch(mfas_population* p, int32_t k, const mfas_table* tab, in
     if (dlogits) {   // 3. dW of every matrix into its m slot (see the header comment); W, v-scaled-by-lr-0 steps leave W as it was
         st.sa.do_update = 1; st.sa.do_forward = 0;
         sweep();
+        tap_grad_launch(pl, p->plane.get(), p->stepbuf.get(), k, nrows, tg, p->stream);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(p->stream));

@@ -566,6 +566,33 @@ class Population:
             _lib.check(self.lib.mfas_population_backward(self._h, k, C.byref(tc), row0, nrows, int(step), C.c_void_p(d.data_ptr())))
         return self.get_params(k, plane=1)
 
+    def backward_taps(self, k: int, table: FeatureTable, dlogits: torch.Tensor, row0: int = 0, nrows: Optional[int] = None, step: int = 0,
+                      taps: Optional[Sequence[str]] = None):
+        """`backward`, and the gradients of the same loss with respect to feature taps (mfas_population_backward_taps): returns
+        (flat, {"s0": tensor, ...}), each tensor (nrows, width) float32 on the device.  taps: the names wanted; None = every tap
+        candidate k selects.  A tap named here that candidate k does not select comes back as zeros; a slot of width 0 is refused."""
+        nrows = len(table) - row0 if nrows is None else nrows
+        self._check_table(table)
+        d = dlogits.to(device=self.device, dtype=torch.float32).contiguous()
+        assert tuple(d.shape) == (nrows, self.hp.C), (tuple(d.shape), (nrows, self.hp.C))
+        if taps is None:
+            taps = sorted({f"s{int(c[0])}" for c in self.confs[k]}) + sorted({f"v{int(c[1])}" for c in self.confs[k]})
+        sizes = {"s": list(self.hp.s_sizes), "v": list(self.hp.v_sizes)}
+        grads, ptrs = {}, {"s": (C.c_void_p * _lib.MAX_TAPS)(), "v": (C.c_void_p * _lib.MAX_TAPS)()}
+        for name in taps:
+            if len(name) < 2 or name[0] not in "sv" or not name[1:].isdigit() or int(name[1:]) >= _lib.MAX_TAPS:
+                raise ValueError(f"unknown tap {name!r}")
+            j = int(name[1:])
+            width = int(sizes[name[0]][j]) if j < len(sizes[name[0]]) else 0
+            # (a slot of width 0 still gets a pointer: the engine refuses it, naming the slot)
+            grads[name] = torch.empty((nrows, width), dtype=torch.float32, device=self.device)
+            ptrs[name[0]][j] = grads[name].data_ptr() if width else d.data_ptr()
+        tc = table.to_c()
+        with torch.cuda.device(self._idx):
+            _lib.check(self.lib.mfas_population_backward_taps(self._h, k, C.byref(tc), row0, nrows, int(step), C.c_void_p(d.data_ptr()),
+                                                              ptrs["s"], ptrs["v"]))
+        return self.get_params(k, plane=1), grads
+
     def set_pos_weight(self, w):
         w = np.ascontiguousarray(np.asarray(w, np.float32))
         assert w.size == self.hp.C

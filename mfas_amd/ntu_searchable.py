@@ -64,7 +64,8 @@ class _TrainModeForward(torch.autograd.Function):
     mfas_population_forward_train on a scratch population holding the module's parameters; backward = mfas_population_backward on
     a scratch population of the same state (same dropout stream, same batch statistics) with the incoming dL/dlogits — the
     engine's own fused backward, not a torch graph.  ntu_searchable.py:206-247 under model.train(True), for callers that write
-    their own loop.  Nothing of the GPU is kept between the two calls (the backward pass runs the batch again anyway): a forward
+    their own loop.  With args.engine_tap_grads the tap tensors that require grad are inputs too, and backward =
+    mfas_population_backward_taps for exactly those taps.  Nothing of the GPU is kept between the two calls (the backward pass runs the batch again anyway): a forward
     under no_grad, or one whose loss is never backpropagated, holds no device memory."""
 
     @staticmethod
@@ -76,7 +77,9 @@ class _TrainModeForward(torch.autograd.Function):
         return pop
 
     @staticmethod
-    def forward(ctx, module, table, n, seed, *params):
+    def forward(ctx, module, table, n, seed, *rest):
+        # rest: the module's parameters, then — engine_tap_grads — a _TapInputs marker and the tap tensors it names
+        mark = next((i for i, r in enumerate(rest) if isinstance(r, _TapInputs)), len(rest))
         flat0 = module.flat_params()
         pop = _TrainModeForward._scratch(module, table, n, seed, flat0)
         try:
@@ -87,14 +90,21 @@ class _TrainModeForward(torch.autograd.Function):
         finally:
             pop.close()
         ctx.table, ctx.n, ctx.seed, ctx.flat0, ctx.module = table, n, seed, flat0, module
+        ctx.tap_names = rest[mark].names if mark < len(rest) else ()
+        ctx.tap_like = [(t.dtype, tuple(t.shape)) for t in rest[mark + 1:]]
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         module = ctx.module
+        want = [name for name, need in zip(ctx.tap_names, ctx.needs_input_grad[-len(ctx.tap_names):]) if need] if ctx.tap_names else []
         pop = _TrainModeForward._scratch(module, ctx.table, ctx.n, ctx.seed, ctx.flat0)     # the state the forward saw
         try:
-            gflat = pop.backward(0, ctx.table, grad_out, 0, ctx.n, step=0).cpu()
+            if want:      # exactly the taps that ask for a gradient (mfas_population_backward_taps)
+                gflat, gtaps = pop.backward_taps(0, ctx.table, grad_out, 0, ctx.n, step=0, taps=want)
+                gflat = gflat.cpu()
+            else:
+                gflat, gtaps = pop.backward(0, ctx.table, grad_out, 0, ctx.n, step=0).cpu(), {}
         finally:
             pop.close()
         where = {key: (shape, off) for key, shape, off in flat_layout(module.conf, module.hyper(False))[0]}
@@ -106,7 +116,18 @@ class _TrainModeForward(torch.autograd.Function):
                 continue
             shape, off = where[key]
             grads.append(gflat[off:off + int(np.prod(shape))].reshape(shape).to(prm.device))
-        return (None, None, None, None, *grads)
+        if not ctx.tap_names:
+            return (None, None, None, None, *grads)
+        # each tap's gradient in the tap's own dtype and shape
+        tap_grads = [gtaps[name].to(dtype).reshape(shape) if name in gtaps else None for name, (dtype, shape) in zip(ctx.tap_names, ctx.tap_like)]
+        return (None, None, None, None, *grads, None, *tap_grads)
+
+
+class _TapInputs:
+    """Marks where the tap tensors begin in _TrainModeForward's arguments, and names them."""
+
+    def __init__(self, names):
+        self.names = tuple(names)
 
 
 # ------------------------------------------------------------------------------------------------ the fusion net
@@ -220,7 +241,8 @@ class Searchable_Skeleton_Image_Net(nn.Module):
         [+ 'slogit'] on a HIP device.  Eval mode: running-statistics BatchNorm, no Dropout (mfas_population_forward).  Train mode:
         one batch of <= 128 samples with batch statistics and Dropout, differentiable with respect to the central parameters
         (_TrainModeForward).  The taps are outputs of frozen backbones here (feature tables): no gradient flows into them, and
-        taps that require grad are refused instead of being silently cut off.  The fast path for training stays
+        taps that require grad are refused instead of being silently cut off — unless args.engine_tap_grads is set (opt-in): then
+        the engine's backward returns their gradients too, each in the tap's own dtype and shape.  The fast path for training stays
         train_sampled_models / train_ntu_track_acc."""
         image, skeleton = tensor_tuple[0], tensor_tuple[1]
         visual = self.rgbnet(image)
@@ -231,9 +253,13 @@ class Searchable_Skeleton_Image_Net(nn.Module):
             raise ValueError("forward needs the pooled taps 'v0'.. / 's0'.. of the batch (there are no backbones in this engine)")
         some = next(iter(taps.values()))
         n = some.shape[0]
-        if self.training and torch.is_grad_enabled() and any(t.requires_grad for t in taps.values()):
+        tap_grads = self.training and torch.is_grad_enabled() and any(t.requires_grad for t in taps.values())
+        if tap_grads and not getattr(self.args, "engine_tap_grads", False):
             raise NotImplementedError("the taps require grad, but this engine's backbones are frozen feature tables: it produces gradients "
                                       "for central_params() only (train_only_central_params, ntu_searchable.py:27); detach() the taps")
+        # (args.engine_tap_grads, opt-in: the engine's backward also returns the gradients of the taps that require grad —
+        #  mfas_population_backward_taps — so the module can sit behind a backbone, adapter or projection that learns)
+        live = {k: v for k, v in taps.items() if v.requires_grad} if tap_grads else {}
         # (eval mode needs no gradient of the taps: the reference's eval forward accepts them, so they are detached silently)
         taps = {k: v.detach() for k, v in taps.items()}
         table = FeatureTable(taps, torch.zeros(n, dtype=torch.int32, device=some.device))
@@ -247,7 +273,8 @@ class Searchable_Skeleton_Image_Net(nn.Module):
             if n == 1 and self.args.batchnorm:
                 raise ValueError("Expected more than 1 value per channel when training")     # torch BatchNorm1d's message
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-            out = _TrainModeForward.apply(self, table, n, seed, *[p for _, p in self.named_parameters()])
+            tap_args = (_TapInputs(live), *live.values()) if live else ()
+            out = _TrainModeForward.apply(self, table, n, seed, *[p for _, p in self.named_parameters()], *tap_args)
             if not self.args.multitask:
                 return out
             return out, visual["vlogit"], skel["slogit"]
